@@ -1,19 +1,28 @@
 #!/usr/bin/env python
 """bench.py — clips/sec of the GaVA-CLIP video-frame forward path on N MI355X GPUs.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 One "step" = one VitaCLIP.forward() (vision tower + text tower + RCCL all-gather of the clip
 embeddings + similarity head) over one synthetic batch of 64 clips per GPU (BASELINE.json
-configs[1] / configs[3]; weak scaling).  Inputs are resident in HBM before the timed region.
-Rank 0 prints ONE JSON line (contract in the task statement), extended with
+configs[1] / configs[3]; weak scaling).  Inputs are resident in HBM before the timed region;
+weights (torch.manual_seed(0)) and inputs (seeded device generator) are the same from run to run.
+A plain run sets up, warms up, times exactly K steps and prints ONE JSON line on rank 0 (metric,
+value, unit, higher_is_better, dtype, ms_per_step, ...).
+  --dump-outputs DIR  after the timed steps, the arrays the last timed step returned
+                      (VitaCLIP.forward: logits, and logits_mt / logits_vm when present)
+                      as DIR/<name>.npy in float32, rank 0 only
+  --full              adds the legs below to the line (each can be left out with its --no-* option)
+  gather        — (N > 1) the all-gather of the clip embeddings timed on its own
   roofline      — the kernel INSTANTIATION with the largest share of the forward's GPU time (out_proj + fc2 of the vision blocks:
                   gemm256_kernel<PrecF16, EPI_F32, RES, ...>) timed stand-alone with HIP events, its members priced on their own roofs
-  cpu_baseline  — the oracle (CPU port of the reference) timed on the host cores, N=1 only
   kernels       — stand-alone HIP-event timings of every hot kernel shape of one layer
-  parity_modes  — clips/s of the weight-lo modes (operand_dtype fp16+wlo8 / fp16+wlo), whose accuracy block sits in `accuracy`
+  alt / parity_modes — clips/s of the other operand dtype and of the weight-lo modes (operand_dtype fp16+wlo8 / fp16+wlo)
+  train_step    — one training step (forward + backward + AdamW) at the same batch, c2 / c3
+  accuracy      — logits vs the reference-run fixtures of tests/golden/, in every operand mode
+  cpu_baseline  — the oracle (CPU port of the reference) timed on the host cores, N=1 only
 """
 import argparse
 import json
@@ -72,13 +81,21 @@ def parse():
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
     ap.add_argument("--prec", default=os.environ.get("GAVA_PREC", "fp16"), choices=["fp16", "bf16", "fp16+wlo", "fp16+wlo8"],
                     help="MFMA operand mode of the timed forward; the +wlo modes are the parity modes (weight-lo pass, DESIGN 'Numerics')")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned to DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: kernel table + roofline, other operand modes, training "
+                         "step, accuracy vs the golden fixtures, CPU baseline (N > 1: the all-gather on its own)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernels", action="store_true", help="skip the stand-alone kernel timings")
     ap.add_argument("--no-alt", action="store_true", help="skip the short run in the other operand dtype")
     ap.add_argument("--no-train", action="store_true", help="skip the training-step measurement")
     ap.add_argument("--no-accuracy", action="store_true", help="skip the logits-vs-reference-golden check")
     ap.add_argument("--accuracy-c5", action="store_true", help="include the full c3 batch and the ViT-L/14 fixtures (c5_clip0, c5_full) in the accuracy leg")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def timed_steps(fn, steps, warmup, dist=None):
@@ -368,6 +385,22 @@ def cpu_baseline():
                        f"{best:.3f} s/forward, torch {torch.__version__} CPU")
 
 
+def dump_outputs(d, arrays):
+    """arrays (name -> tensor or None) as d/<name>.npy in float32; the forward's outputs are a few hundred logits per
+    clip at most, far below the 64 MB the dump may take."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        arr = t.detach().float().cpu().numpy()
+        total += arr.nbytes
+        assert total <= 64 << 20, f"outputs exceed 64 MB ({total} bytes)"
+        np.save(os.path.join(d, name + ".npy"), arr)
+        log(f"wrote {os.path.join(d, name + '.npy')} {arr.shape}")
+
+
 def main():
     a = parse()
     rank = int(os.environ.get("RANK", "0"))
@@ -405,19 +438,26 @@ def main():
         with torch.no_grad():
             return model(x)
 
+    last = {}
+
+    def timed_step():
+        last["out"] = step()                  # what the last timed step returned: checked, and dumped with --dump-outputs
+
     log("model on device; first forward (packs weights)")
     step(); torch.cuda.synchronize()
     log("timed region")
-    secs = timed_steps(step, a.steps, a.warmup, dist)
+    secs = timed_steps(timed_step, a.steps, a.warmup, dist)
     log(f"{a.steps} steps in {secs:.3f}s")
-    logits = step()[0]
+    logits = last["out"][0]
     assert tuple(logits.shape) == (B * world, n_cls) and bool(torch.isfinite(logits).all())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, dict(zip(("logits", "logits_mt", "logits_vm"), last["out"])))
     clips = world * B * a.steps
     value = clips / secs
     fwd_flops = fl.forward_flops(cfg, B, n_cls)
     exe_flops = fl.executed_flops(cfg, B, n_cls, text_rows=model.text_rows_per_prompt)
     gather = None
-    if dist is not None:
+    if dist is not None and a.full:
         # the path's only exchange on its own: event pair (time.perf_counter for a CPU rendezvous) around 20 all-gathers of
         # the (B, E) clip embeddings, every rank taking part; max over ranks
         feats = torch.randn(B, cfg.embed_dim, device="cuda")
@@ -433,6 +473,7 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         gather = {"ms": round(float(t.item()), 4), "bytes_per_rank": B * cfg.embed_dim * 4, "backend": dist.get_backend(),
                   "what": "all_gather_into_tensor of the (B, E) fp32 clip embeddings, 20 back-to-back, host clock incl. launch, max over ranks"}
+    if dist is not None:
         # No rank may sit in a collective while rank 0 measures alone: the group is torn down HERE, before any rank-0-only
         # leg, and every other rank leaves.  (The rank-0-only legs - kernel table, roofline, other dtype, training step,
         # accuracy, CPU baseline - belong to the N = 1 line and are skipped for N > 1.)
@@ -466,7 +507,7 @@ def main():
     }
     if gather is not None:
         out["gather"] = gather
-    solo = world == 1      # the legs below run on one rank alone: N = 1 only
+    solo = world == 1 and a.full      # the legs below run on one rank alone: N = 1 only, and with --full only
     if solo and not a.no_kernels:
         log("stand-alone kernel timings")
         fold = bool(getattr(model, "fold_layernorm", False))
@@ -600,7 +641,7 @@ def main():
                 s3 = timed_steps(step, n_, 2, None)
                 out["parity_modes"][mode] = {"value": round(B * n_ / s3, 2), "unit": "clips/s", "ms_per_step": round(1e3 * s3 / n_, 3)}
             model.set_operand_dtype(a.prec)
-    if rank == 0 and world == 1 and not a.no_train and a.config in ("c2", "c3"):
+    if rank == 0 and solo and not a.no_train and a.config in ("c2", "c3"):
         # one training step (forward with saved block inputs, loss.backward() through the HIP
         # backward kernels, AdamW on the trainable subset), same batch.  Reported beside the headline, not part of it.
         log("training step")
@@ -623,9 +664,9 @@ def main():
             out["train_roofline"] = train_roofline(cfg, B)
         except Exception as e:   # evidence leg: must never break the bench line
             log(f"train_roofline skipped: {e}")
-    if rank == 0 and world == 1 and cname == "VIT_B16_T8" and not a.no_accuracy:
+    if rank == 0 and solo and cname == "VIT_B16_T8" and not a.no_accuracy:
         out["accuracy"] = accuracy_vs_golden(a.prec, include_c5=a.accuracy_c5)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and solo and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline()
     if rank == 0:
         print(json.dumps(out))

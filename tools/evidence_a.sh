@@ -9,11 +9,11 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   timeout -k 10 1500 python -m pytest tests -q -m gpu > $O/gpu_tests.log 2>&1; tail -3 $O/gpu_tests.log
 fi
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
-timeout -k 10 900 python bench.py > $O/bench_c2.json 2> $O/bench_c2.err || tail -20 $O/bench_c2.err
-timeout -k 10 400 python bench.py --config c3 --steps 20 --warmup 5 --no-cpu-baseline --no-alt > $O/bench_c3.json 2> $O/bench_c3.err || tail -5 $O/bench_c3.err
-timeout -k 10 400 python bench.py --config c5 --steps 10 --warmup 3 --no-cpu-baseline --no-alt > $O/bench_c5.json 2> $O/bench_c5.err || tail -5 $O/bench_c5.err
+timeout -k 10 900 python bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err || tail -20 $O/bench_c2.err
+timeout -k 10 400 python bench.py --full --config c3 --steps 20 --warmup 5 --no-cpu-baseline --no-alt > $O/bench_c3.json 2> $O/bench_c3.err || tail -5 $O/bench_c3.err
+timeout -k 10 400 python bench.py --full --config c5 --steps 10 --warmup 3 --no-cpu-baseline --no-alt > $O/bench_c5.json 2> $O/bench_c5.err || tail -5 $O/bench_c5.err
 GAVA_DIST_BACKEND=gloo HSA_ENABLE_IPC_MODE_LEGACY=0 timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 \
-  bench.py --gpus 2 --steps 10 --warmup 3 > $O/bench_c2_2rank_gloo.json 2> $O/bench_c2_2rank_gloo.err || tail -20 $O/bench_c2_2rank_gloo.err
+  bench.py --full --gpus 2 --steps 10 --warmup 3 > $O/bench_c2_2rank_gloo.json 2> $O/bench_c2_2rank_gloo.err || tail -20 $O/bench_c2_2rank_gloo.err
 python - <<PY
 import json
 for c in ("c2", "c3", "c5", "c2_2rank_gloo"):
