@@ -429,15 +429,17 @@ int gava_vision_forward_train(const gava_vision_model* m, const float* x, float*
 
 /* Training forward that keeps the backward's activations instead of leaving them to be recomputed.  With
  * R = B*T_in*(n+1), SR = G + 2*B*T_in:  e0 fp32 [R][D] (embedding before ln_pre);  x fp32 [layers+1][R][D] (block inputs,
- * last slot = final stream);  x1 fp32 [layers][R][D] (stream after the attention branch);  qkv h16 [layers][R][3D];
- * pre h16 [layers][R][F] (fc1 output before QuickGELU);  sidekv h16 [layers][SR][2D] (prompt-row keys/values).
+ * last slot = final stream);  x1 fp32 [L1][R][D] (stream after the attention branch);  qkv h16 [layers][R][3D];
+ * pre h16 [L1][R][F] (fc1 output before QuickGELU);  sidekv h16 [layers][SR][2D] (prompt-row keys/values).
+ * L1 = layers when last_* (below) are NULL; with last_* the last block's x1 / pre slot is never touched, so L1 = layers-1
+ * slots suffice (at least one: the pointers must not be NULL).  training.alloc_kept allocates max(layers-1, 1).
  * Nothing is copied: the residual stream hops x[i] -> x1[i] -> x[i+1]. */
 typedef struct {
   float* e0; float* x; float* x1; void* qkv; void* pre; void* sidekv;
   /* optional (all three or none): run the LAST block on the CLS rows only, as gava_vision_forward does, and keep its
    * CLS-row activations here: last_q h16 [B*T_in][D] (scaled queries), last_x1 fp32 [B*T_in][D], last_pre h16
-   * [B*T_in][F].  The block's K/V then sit in columns D..3D of its qkv slot; x1 / pre of that block are unused and only
-   * the CLS rows of the final stream are written. */
+   * [B*T_in][F].  The block's K/V then sit in columns D..3D of its qkv slot (its q columns are not written); x1 / pre
+   * have no slot for that block, and only the CLS rows of the final stream x[layers] are written. */
   void* last_q; float* last_x1; void* last_pre;
 } gava_vision_saved;
 int gava_vision_forward_keep(const gava_vision_model* m, const float* x, float* cls_x, float* summary,
