@@ -6,7 +6,7 @@ Only the prompt-enabled configuration is valid in the reference (SURVEY.md §7,
 hard part 5: the non-global-prompt branch is broken upstream), so summary token,
 local prompts and global prompts are always on here.
 """
-from dataclasses import dataclass, asdict
+from dataclasses import dataclass, asdict, replace
 from collections import OrderedDict
 
 
@@ -125,3 +125,10 @@ def param_shapes(cfg: VitaConfig, n_cls: int) -> "OrderedDict[str, tuple]":
     s["textual.ln_final.bias"] = (W,)
     s["prompt_learner.ctx"] = (n_cls, cfg.text_num_prompts, W)
     return s
+
+# shapes past the 320-key class of the single-pass attention kernels (key-streaming kernels, attention.hip /
+# attention_bwd.hip): keys per frame = patches + 1 + G + T + 1
+TINY_T320 = replace(TINY, num_frames=320)                        # 16 + 1 + 4 + 320 + 1 = 342 keys, T = 320 summary keys
+TINY_320PX = replace(TINY, input_size=320)                       # 400 + 1 + 4 + 4 + 1 = 410 keys, 401 queries
+VIT_L14_T64 = replace(VIT_L14_T32, num_frames=64)                # 330 keys
+VIT_B16_T128 = VitaConfig(num_frames=128)                        # 334 keys

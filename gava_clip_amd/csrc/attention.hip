@@ -620,11 +620,201 @@ __global__ __launch_bounds__(512, 1) void attention_persist_kernel(const AttnPar
 #undef PSTAMP
 }
 
+// ---------------------------------------------------------------------------------------------
+// Key-streaming (online-softmax) form for key sets the single-pass kernels above cannot hold (> 320 keys: ViT-L/14 past 54
+// frames, ViT-B/16 past 114, 336/384 px inputs with 577 queries), and the T-token summary attention once T > 320.
+// Grid (problem, group of NWV query tiles): each wave owns one 16-query tile for the whole key walk, so its running max,
+// row sum and O^T accumulators stay in registers.  K/V arrive in blocks of SKB keys, double-buffered in LDS by LDS-DMA
+// (the same swizzled 128-byte rows and the same fragment addresses as above: a block starts at a multiple of 8 rows, so the
+// swizzle of a row is the same in block and problem coordinates); block b+1 is in flight while block b is computed, one
+// barrier per block.  Per block: S^T = K Q^T (key on the MFMA row), block max, rescale factor alpha = exp(m_old - m_new),
+// P = exp(s - m_new) straight from the accumulators as the B operand of O^T = V^T P^T, and the row sum by the all-ones MFMA
+// row (ONESUM) so that it sums the rounded P the numerator uses; O^T and the sum are scaled by alpha before the block's
+// products are added.  Only the last block can hold invalid keys (rows past n_keys, staged as copies of row 0), and only
+// it carries the mask.
+constexpr int SKB = 128;   // keys per streamed block: 2 x 2 x 16 KiB of LDS per workgroup, two workgroups per CU
+
+// source of key row `row` of problem n: the frame's own rows, then G global | the clip's T local | the frame's summary row
+__device__ __forceinline__ long kv_src_off(const AttnParams& p, int n, int h, int row, int chunk, bool& is_main) {
+  const int rowc = row < p.n_keys ? row : 0;
+  const int sidx = rowc - p.n_kmain;
+  const long sr = sidx < p.n_g ? sidx
+                : sidx < p.n_g + p.T ? p.n_g + (long)(n / p.T) * p.T + (sidx - p.n_g)
+                                     : (long)p.n_g + p.batch + n;
+  is_main = rowc < p.n_kmain;
+  return (is_main ? ((long)n * p.n_kmain + rowc) * p.ld : sr * p.lds) + h * 64 + chunk * 8;
+}
+
+template <int NTH>
+__device__ __forceinline__ void stage_kv_block(const AttnParams& p, int n, int h, int kb0, char* Ks, char* Vs, int tid, int wave) {
+  static_assert(SKB * 8 % NTH == 0, "whole waves per block");
+#pragma unroll
+  for (int it = 0; it < SKB * 8 / NTH; ++it) {
+    const int id = tid + it * NTH;
+    const int row = id >> 3, chunk = (id & 7) ^ (row & 6);
+    bool is_main;
+    const long off = kv_src_off(p, n, h, kb0 + row, chunk, is_main);
+    // pointer selects as integers: selected as pointers, the pair {k, sk} goes to a scratch array indexed by is_main
+    const unsigned long kb = is_main ? (unsigned long)p.k : (unsigned long)p.sk;
+    const unsigned long vb = is_main ? (unsigned long)p.v : (unsigned long)p.sv;
+    const int dst = (wave * 64 + it * NTH) * 16;
+    dma16(reinterpret_cast<const unsigned short*>(kb) + off, lds_addr(Ks) + dst);
+    dma16(reinterpret_cast<const unsigned short*>(vb) + off, lds_addr(Vs) + dst);
+  }
+}
+
+template <class P, int NWV>
+__global__ __launch_bounds__(NWV * 64, 2) void attention_stream_kernel(const AttnParams p) {
+  constexpr int NKT = SKB / 16;
+  constexpr int BUF = SKB * LDS_ROW;
+  __shared__ __attribute__((aligned(16))) char Ks[2 * BUF];
+  __shared__ __attribute__((aligned(16))) char Vs[2 * BUF];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int n = blockIdx.x / p.heads, h = blockIdx.x - n * p.heads;
+  const int fr = lane & 15, fg = lane >> 4;
+  const int n_qt = (p.n_q + 15) >> 4;
+  const int qt = blockIdx.y * NWV + wave;
+  const bool active = qt < n_qt;                        // wave-uniform; idle waves still stage and meet the barriers
+  const int qi = qt * 16 + fr;
+  const int n_kb = (p.n_keys + SKB - 1) / SKB;
+
+  const unsigned short* qp = q_row_ptr(p, n, h, active ? qt : 0, fr, fg);   // clamped to a valid row
+  const s16x8_t q0 = *reinterpret_cast<const s16x8_t*>(qp);
+  const s16x8_t q1 = *reinterpret_cast<const s16x8_t*>(qp + 32);
+  stage_kv_block<NWV * 64>(p, n, h, 0, Ks, Vs, tid, wave);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+
+  const FragAddr fa = frag_addr(fr, fg);
+  const unsigned short one = P::cvt(1.0f);
+  const s16x8_t ones = {(short)one, (short)one, (short)one, (short)one, (short)one, (short)one, (short)one, (short)one};
+  f32x4_t o[4], os = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) o[dt] = os;
+  float m = -INFINITY;
+  int lane_key = 4 * fg;
+
+  for (int kb = 0; kb < n_kb; ++kb) {
+    const int buf = kb & 1;
+    // the other buffer was last read before the previous barrier
+    if (kb + 1 < n_kb) stage_kv_block<NWV * 64>(p, n, h, (kb + 1) * SKB, Ks + (buf ^ 1) * BUF, Vs + (buf ^ 1) * BUF, tid, wave);
+    if (active) {
+      const char* ks = Ks + buf * BUF;
+      const char* vs = Vs + buf * BUF;
+      f32x4_t s[NKT];
+      constexpr int QCH = NKT / 2;
+#pragma unroll
+      for (int c0 = 0; c0 < NKT; c0 += QCH) {
+        s16x8_t kf[QCH][2];
+#pragma unroll
+        for (int t = 0; t < QCH; ++t) {
+          kf[t][0] = *reinterpret_cast<const s16x8_t*>(ks + fa.k0 + (c0 + t) * 16 * LDS_ROW);
+          kf[t][1] = *reinterpret_cast<const s16x8_t*>(ks + fa.k1 + (c0 + t) * 16 * LDS_ROW);
+        }
+#pragma unroll
+        for (int t = 0; t < QCH; ++t) {
+          f32x4_t a = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+          a = P::mfma(kf[t][0], q0, a);
+          a = P::mfma(kf[t][1], q1, a);
+          s[c0 + t] = a;
+        }
+        __builtin_amdgcn_sched_group_barrier(0x100, 2 * QCH, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 2 * QCH, 0);
+      }
+      if (kb * SKB + SKB > p.n_keys) {                  // the last block: mask the keys past n_keys
+        asm volatile("" : "+v"(lane_key));
+#pragma unroll
+        for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            s[kt][r] = kb * SKB + kt * 16 + lane_key + r < p.n_keys ? s[kt][r] : -INFINITY;
+      }
+      float bm = -INFINITY;
+#pragma unroll
+      for (int kt = 0; kt < NKT; ++kt) bm = fmaxf(fmaxf(bm, s[kt][0]), fmaxf(s[kt][1], fmaxf(s[kt][2], s[kt][3])));
+      const float mn = fmaxf(m, max_across_lane_groups(bm));
+      // m == mn covers -inf == -inf (nothing valid seen yet: the accumulators are 0 and stay so); m = -inf alone gives 0
+      const float alpha = m == mn ? 1.f : __builtin_amdgcn_exp2f((m - mn) * LOG2E);
+      const float mneg = mn == -INFINITY ? 0.f : -mn * LOG2E;
+      m = mn;
+#pragma unroll
+      for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) s[kt][r] = __builtin_amdgcn_exp2f(fmaf(s[kt][r], LOG2E, mneg));
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        os[r] *= alpha;
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) o[dt][r] *= alpha;
+      }
+      constexpr int NC2 = NKT / 2, PCH = 2;
+#pragma unroll
+      for (int b0 = 0; b0 < NC2; b0 += PCH) {
+        s16x4_t t0[PCH][4], t1[PCH][4];
+#pragma unroll
+        for (int c = 0; c < PCH; ++c)
+#pragma unroll
+          for (int dt = 0; dt < 4; ++dt) {
+            const char* vb = vs + fa.v[dt] + (b0 + c) * 32 * LDS_ROW;
+            t0[c][dt] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4_t, vb));
+            t1[c][dt] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4_t, vb + 16 * LDS_ROW));
+          }
+#pragma unroll
+        for (int c = 0; c < PCH; ++c) {
+          const int cc = b0 + c;
+          const uint2 lo = pack4<P>(s[2 * cc][0], s[2 * cc][1], s[2 * cc][2], s[2 * cc][3]);
+          const uint2 hi = pack4<P>(s[2 * cc + 1][0], s[2 * cc + 1][1], s[2 * cc + 1][2], s[2 * cc + 1][3]);
+          const s16x8_t pf = __builtin_bit_cast(s16x8_t, make_uint4(lo.x, lo.y, hi.x, hi.y));
+#pragma unroll
+          for (int dt = 0; dt < 4; ++dt)
+            o[dt] = P::mfma(__builtin_shufflevector(t0[c][dt], t1[c][dt], 0, 1, 2, 3, 4, 5, 6, 7), pf, o[dt]);
+          os = P::mfma(ones, pf, os);
+        }
+      }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // block kb+1 has landed (this thread's part) ...
+    __builtin_amdgcn_s_barrier();                      // ... everyone's, and nobody reads buffer `buf` any more
+    asm volatile("" ::: "memory");
+  }
+  if (active && qi < p.n_q) {
+    const float inv = __builtin_amdgcn_rcpf(os[0]);
+    unsigned short* op = p.out + ((long)n * p.n_q + qi) * p.ldo + h * 64 + 4 * fg;
+    const int Dm = p.heads * 64;
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+      if (p.split) {
+        uint2 hi, lo;
+        split4<P>(o[dt][0] * inv, o[dt][1] * inv, o[dt][2] * inv, o[dt][3] * inv, hi, lo);
+        *reinterpret_cast<uint2*>(op + dt * 16) = hi;
+        *reinterpret_cast<uint2*>(op + dt * 16 + Dm) = lo;
+        *reinterpret_cast<uint2*>(op + dt * 16 + 2 * Dm) = hi;
+      } else {
+        *reinterpret_cast<uint2*>(op + dt * 16) = pack4<P>(o[dt][0] * inv, o[dt][1] * inv, o[dt][2] * inv, o[dt][3] * inv);
+      }
+    }
+  }
+}
+
+// GAVA_ATTN_STREAM=1 sends every non-causal shape to the streaming kernels (forward and backward; A/B and tests).
+bool stream_forced() {
+  static const bool on = getenv("GAVA_ATTN_STREAM") && getenv("GAVA_ATTN_STREAM")[0] == '1';
+  return on;
+}
+
 template <class P>
 int launch_attn(const AttnParams& p, hipStream_t s) {
   const int n_prob = p.batch * p.heads;
   dim3 grid(n_prob), blk(256);
   const int tiles = (p.n_keys + 15) / 16;
+  if (!p.causal && (tiles > 20 || stream_forced())) {
+    constexpr int NWV = 4;
+    const int n_qt = (p.n_q + 15) / 16;
+    hipLaunchKernelGGL((attention_stream_kernel<P, NWV>), dim3(n_prob, (n_qt + NWV - 1) / NWV), dim3(NWV * 64), 0, s, p);
+    GAVA_CHECK_LAUNCH();
+    return GAVA_OK;
+  }
   // two query tiles per wave for the big non-causal problems (vision blocks); GAVA_ATTN_PAIR=0 turns it off (A/B)
   static const bool pair_ok = !(getenv("GAVA_ATTN_PAIR") && getenv("GAVA_ATTN_PAIR")[0] == '0');
   const bool pair = pair_ok && !p.causal && !p.split && p.n_q >= 64;
@@ -794,7 +984,7 @@ extern "C" int gava_attention(const gava_attention_args* a, gava_stream_t stream
   p.qbr = a->q_batch_rows > 0 ? a->q_batch_rows : a->n_q;
   p.ldq = a->ld_q > 0 ? a->ld_q : a->ld_qkv;
   if (p.ldq % 8 || p.qbr < a->n_q) return GAVA_EINVAL;
-  if (p.n_keys > 320) return GAVA_EINVAL;
+  if (p.causal && p.n_keys > 320) return GAVA_EINVAL;   // causal (text tower, L <= 77) has no streaming form
   hipStream_t s = (hipStream_t)stream;
   if (a->prec == GAVA_PREC_F16) return launch_attn<PrecF16>(p, s);
   if (a->prec == GAVA_PREC_BF16) return launch_attn<PrecBF16>(p, s);

@@ -368,16 +368,332 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const gava::AttnBw
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Streaming forms for the shapes the kernels above cannot hold (non-causal only): more than 320 keys (dQ kernel: all
+// scores of a tile in registers) or more than 288 queries (dK/dV kernel: all of Q and dO in LDS).  Each workgroup owns 4
+// tiles (one per wave) for the whole walk over the other side, which arrives in blocks of SB rows through LDS (padded
+// 160-byte rows as above); the next block's rows are loaded into registers while the current one is computed.
+constexpr int SB = 128;
+
+// dQ, keys streamed in two passes over the key blocks:
+//   pass 1: S^T and dP^T per block; running max m, sum l = sum exp(s - m) and delta' = sum exp(s - m) dP, both rescaled
+//           when m moves; at the end L2 = m log2e + log2 l and delta = delta' / l (the row statistics of the dK/dV kernel)
+//   pass 2: S^T and dP^T again, P = exp2(s log2e - L2), dS^T = P^T * (dP^T - delta), dQ^T += K^T dS^T
+// so that dS is formed in fp32 and rounded once, as in attn_bwd_dq_kernel.
+template <class P, class PA>
+__global__ __launch_bounds__(256, 2) void attn_bwd_dq_stream_kernel(const gava::AttnBwdMfmaParams p) {
+  constexpr int NKT = SB / 16;
+  constexpr int NIT = SB * 8 / 256;
+  __shared__ __attribute__((aligned(16))) char smem[2 * SB * LDS_ROW];
+  char* Ks = smem;
+  char* Vs = smem + SB * LDS_ROW;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int n = blockIdx.x / p.heads, h = blockIdx.x - n * p.heads;
+  const int fr = lane & 15, fg = lane >> 4;
+  const int n_qt = (p.n_q + 15) >> 4;
+  const int qt = blockIdx.y * 4 + wave;
+  const bool active = qt < n_qt;                       // wave-uniform; idle waves still stage and meet the barriers
+  const int qi = qt * 16 + fr;
+  const int qrow = qi < p.n_q ? qi : p.n_q - 1;
+  const long row0 = (long)n * p.n_kmain, qrow0 = (long)n * p.q_rows;
+  const int n_kb = (p.n_keys + SB - 1) / SB;
+
+  const unsigned short* qp = p.q + (qrow0 + qrow) * p.ld_q + h * 64 + 8 * fg;
+  const unsigned short* gp = p.dout + (qrow0 + qrow) * p.ld_dout + h * 64 + 8 * fg;
+  const s16x8_t q0 = load_act8<PA, P>(qp), q1 = load_act8<PA, P>(qp + 32);
+  const s16x8_t g0 = *reinterpret_cast<const s16x8_t*>(gp), g1 = *reinterpret_cast<const s16x8_t*>(gp + 32);
+
+  uint4 kv[NIT], vv[NIT];
+  auto load_block = [&](int kb) {
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      const int id = tid + it * 256;
+      const int key = kb * SB + (id >> 3), chunk = id & 7;
+      const int keyc = key < p.n_keys ? key : 0;
+      const bool is_main = keyc < p.n_kmain;
+      const long off = (is_main ? (row0 + keyc) * p.ld_qkv : side_row_of(p, n, keyc - p.n_kmain) * p.ld_side) + h * 64 + chunk * 8;
+      kv[it] = *reinterpret_cast<const uint4*>((is_main ? p.k : p.sk) + off);
+      vv[it] = *reinterpret_cast<const uint4*>((is_main ? p.v : p.sv) + off);
+    }
+  };
+  load_block(0);
+  const int tr_off = (4 * fg + (fr >> 2)) * LDS_ROW + (fr & 3) * 8;
+  float m = -INFINITY, l = 0.f, dl = 0.f;   // l, dl: this lane's partial sums (its 4 keys per tile)
+  float L2 = 0.f, delta = 0.f;
+  f32x4_t o[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) o[dt] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+
+  for (int it = 0; it < 2 * n_kb; ++it) {
+    const int kb = it < n_kb ? it : it - n_kb;
+    const bool pass2 = it >= n_kb;
+    __syncthreads();                                   // the previous block is read by everyone
+#pragma unroll
+    for (int i = 0; i < NIT; ++i) {
+      const int id = tid + i * 256;
+      const int row = id >> 3, chunk = id & 7;
+      const bool ok = kb * SB + row < p.n_keys;
+      *reinterpret_cast<uint4*>(Ks + row * LDS_ROW + chunk * 16) = ok ? to_p<PA, P>(kv[i]) : make_uint4(0, 0, 0, 0);
+      *reinterpret_cast<uint4*>(Vs + row * LDS_ROW + chunk * 16) = ok ? to_p<PA, P>(vv[i]) : make_uint4(0, 0, 0, 0);
+    }
+    __syncthreads();
+    if (it + 1 < 2 * n_kb) load_block(it + 1 < n_kb ? it + 1 : it + 1 - n_kb);   // in flight under this block's work
+    if (!active) continue;
+
+    f32x4_t s[NKT], dp[NKT];
+#pragma unroll
+    for (int t = 0; t < NKT; ++t) {
+      const int ro = (t * 16 + fr) * LDS_ROW + fg * 16;
+      const s16x8_t k0 = *reinterpret_cast<const s16x8_t*>(Ks + ro), k1 = *reinterpret_cast<const s16x8_t*>(Ks + ro + 64);
+      const s16x8_t v0 = *reinterpret_cast<const s16x8_t*>(Vs + ro), v1 = *reinterpret_cast<const s16x8_t*>(Vs + ro + 64);
+      f32x4_t a = (f32x4_t){0.f, 0.f, 0.f, 0.f}, b = a;
+      a = P::mfma(k0, q0, a);
+      a = P::mfma(k1, q1, a);
+      b = P::mfma(v0, g0, b);
+      b = P::mfma(v1, g1, b);
+      s[t] = a;
+      dp[t] = b;
+    }
+    if (kb * SB + SB > p.n_keys) {                     // the last block: mask the keys past n_keys
+#pragma unroll
+      for (int t = 0; t < NKT; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) s[t][r] = kb * SB + t * 16 + 4 * fg + r < p.n_keys ? s[t][r] : -INFINITY;
+    }
+    if (!pass2) {
+      float bm = -INFINITY;
+#pragma unroll
+      for (int t = 0; t < NKT; ++t) bm = fmaxf(fmaxf(bm, s[t][0]), fmaxf(s[t][1], fmaxf(s[t][2], s[t][3])));
+      bm = fmaxf(bm, __shfl_xor(bm, 16, 64));
+      bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
+      const float mn = fmaxf(m, bm);
+      const float alpha = m == mn ? 1.f : __builtin_amdgcn_exp2f((m - mn) * LOG2E);
+      const float mneg = mn == -INFINITY ? 0.f : -mn * LOG2E;
+      m = mn;
+      l *= alpha; dl *= alpha;
+#pragma unroll
+      for (int t = 0; t < NKT; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float e = __builtin_amdgcn_exp2f(fmaf(s[t][r], LOG2E, mneg));
+          l += e;
+          dl += e * dp[t][r];
+        }
+      if (kb == n_kb - 1) {                            // end of pass 1: the row statistics
+        float lt = l + __shfl_xor(l, 16, 64);
+        lt += __shfl_xor(lt, 32, 64);
+        float dt_ = dl + __shfl_xor(dl, 16, 64);
+        dt_ += __shfl_xor(dt_, 32, 64);
+        L2 = m * LOG2E + __builtin_amdgcn_logf(lt);
+        delta = dt_ * __builtin_amdgcn_rcpf(lt);
+        if (fg == 0 && qi < p.n_q) {
+          float* st = p.stats + ((long)blockIdx.x * p.q_pad + qi) * 2;
+          st[0] = L2;
+          st[1] = delta;
+        }
+      }
+      continue;
+    }
+#pragma unroll
+    for (int c = 0; c < NKT / 2; ++c) {
+      s16x4_t t0[4], t1[4];
+      const char* kb_ = Ks + c * 32 * LDS_ROW + tr_off;
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) {
+        t0[dt] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4_t, kb_ + dt * 32));
+        t1[dt] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4_t, kb_ + 16 * LDS_ROW + dt * 32));
+      }
+      float d[8];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        d[r] = __builtin_amdgcn_exp2f(fmaf(s[2 * c][r], LOG2E, -L2)) * (dp[2 * c][r] - delta);
+        d[4 + r] = __builtin_amdgcn_exp2f(fmaf(s[2 * c + 1][r], LOG2E, -L2)) * (dp[2 * c + 1][r] - delta);
+      }
+      const uint2 lo = pack4<P>(d[0], d[1], d[2], d[3]);
+      const uint2 hi = pack4<P>(d[4], d[5], d[6], d[7]);
+      const s16x8_t df = __builtin_bit_cast(s16x8_t, make_uint4(lo.x, lo.y, hi.x, hi.y));
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt)
+        o[dt] = P::mfma(__builtin_shufflevector(t0[dt], t1[dt], 0, 1, 2, 3, 4, 5, 6, 7), df, o[dt]);
+    }
+  }
+  if (active && qi < p.n_q) {
+    unsigned short* dq = p.dq + (qrow0 + qi) * p.ld_dq + h * 64 + 4 * fg;
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt)
+      *reinterpret_cast<uint2*>(dq + dt * 16) = pack4<P>(o[dt][0] * p.q_scale, o[dt][1] * p.q_scale, o[dt][2] * p.q_scale, o[dt][3] * p.q_scale);
+  }
+}
+
+// dK/dV, queries streamed: each wave owns one 16-key tile (dK^T, dV^T accumulators in registers) and walks the query blocks;
+// per block the same products as attn_bwd_dkv_kernel.  Rows past n_q are zero with L2 = +inf (P = 0).
+template <class P, class PA>
+__global__ __launch_bounds__(256, 2) void attn_bwd_dkv_stream_kernel(const gava::AttnBwdMfmaParams p) {
+  constexpr int NIT = SB * 8 / 256;
+  __shared__ __attribute__((aligned(16))) char smem[2 * SB * LDS_ROW + 2 * SB * sizeof(float)];
+  char* Qs = smem;
+  char* Os = smem + SB * LDS_ROW;
+  float* L2s = reinterpret_cast<float*>(smem + 2 * SB * LDS_ROW);
+  float* Dls = L2s + SB;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int n = blockIdx.x / p.heads, h = blockIdx.x - n * p.heads;
+  const int fr = lane & 15, fg = lane >> 4;
+  const long row0 = (long)n * p.n_kmain;
+  const int n_kt = (p.n_keys + 15) >> 4;
+  const int n_side = p.n_keys - p.n_kmain;
+  const int kt = blockIdx.y * 4 + wave;
+  const bool active = kt < n_kt;
+  const int n_qb = (p.n_q + SB - 1) / SB;
+
+  uint4 qv[NIT], ov[NIT];
+  float l2v = 0.f, dlv = 0.f;
+  auto load_block = [&](int qb) {
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      const int id = tid + it * 256;
+      const int row = qb * SB + (id >> 3), chunk = id & 7;
+      const int rowc = row < p.n_q ? row : 0;
+      qv[it] = *reinterpret_cast<const uint4*>(p.q + ((long)n * p.q_rows + rowc) * p.ld_q + h * 64 + chunk * 8);
+      ov[it] = *reinterpret_cast<const uint4*>(p.dout + ((long)n * p.q_rows + rowc) * p.ld_dout + h * 64 + chunk * 8);
+    }
+    if (tid < SB) {
+      const int qx = qb * SB + tid;
+      const float* st = p.stats + ((long)blockIdx.x * p.q_pad + (qx < p.n_q ? qx : 0)) * 2;
+      l2v = st[0]; dlv = st[1];
+    }
+  };
+  load_block(0);
+
+  const int key = kt * 16 + fr;
+  const bool key_ok = key < p.n_keys;
+  const int keyc = key_ok ? key : 0;
+  const bool is_main = keyc < p.n_kmain;
+  const long koff = (is_main ? (row0 + keyc) * p.ld_qkv : side_row_of(p, n, keyc - p.n_kmain) * p.ld_side) + h * 64 + 8 * fg;
+  const unsigned short* kp = (is_main ? p.k : p.sk) + koff;
+  const unsigned short* vp = (is_main ? p.v : p.sv) + koff;
+  const s16x8_t kb0 = load_act8<PA, P>(kp), kb1 = load_act8<PA, P>(kp + 32);
+  const s16x8_t vb0 = load_act8<PA, P>(vp), vb1 = load_act8<PA, P>(vp + 32);
+  f32x4_t dv[4], dk[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) { dv[dt] = (f32x4_t){0.f, 0.f, 0.f, 0.f}; dk[dt] = dv[dt]; }
+  const int tr_off = (4 * fg + (fr >> 2)) * LDS_ROW + (fr & 3) * 8;
+
+  for (int qb = 0; qb < n_qb; ++qb) {
+    __syncthreads();                                   // the previous block is read by everyone
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      const int id = tid + it * 256;
+      const int row = id >> 3, chunk = id & 7;
+      const bool ok = qb * SB + row < p.n_q;
+      *reinterpret_cast<uint4*>(Qs + row * LDS_ROW + chunk * 16) = ok ? to_p<PA, P>(qv[it]) : make_uint4(0, 0, 0, 0);
+      *reinterpret_cast<uint4*>(Os + row * LDS_ROW + chunk * 16) = ok ? ov[it] : make_uint4(0, 0, 0, 0);
+    }
+    if (tid < SB) {
+      const bool ok = qb * SB + tid < p.n_q;
+      L2s[tid] = ok ? l2v : INFINITY;
+      Dls[tid] = ok ? dlv : 0.f;
+    }
+    __syncthreads();
+    if (qb + 1 < n_qb) load_block(qb + 1);             // in flight under this block's work
+    if (!active) continue;
+    const int nc = (min(SB, p.n_q - qb * SB) + 31) >> 5;   // query-tile pairs of this block that hold a valid query
+#pragma unroll 1
+    for (int c = 0; c < nc; ++c) {
+      f32x4_t st[2], pt[2];
+      s16x4_t oT0[4], oT1[4], qT0[4], qT1[4];
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const int ro = ((2 * c + t) * 16 + fr) * LDS_ROW + fg * 16;
+        const s16x8_t qa0 = *reinterpret_cast<const s16x8_t*>(Qs + ro), qa1 = *reinterpret_cast<const s16x8_t*>(Qs + ro + 64);
+        const s16x8_t oa0 = *reinterpret_cast<const s16x8_t*>(Os + ro), oa1 = *reinterpret_cast<const s16x8_t*>(Os + ro + 64);
+        f32x4_t a = (f32x4_t){0.f, 0.f, 0.f, 0.f}, b = a;
+        a = P::mfma(qa0, kb0, a);
+        a = P::mfma(qa1, kb1, a);
+        b = P::mfma(oa0, vb0, b);
+        b = P::mfma(oa1, vb1, b);
+        st[t] = a;
+        pt[t] = b;
+      }
+      {
+        const char* ob = Os + c * 32 * LDS_ROW + tr_off;
+        const char* qb_ = Qs + c * 32 * LDS_ROW + tr_off;
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+          oT0[dt] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4_t, ob + dt * 32));
+          oT1[dt] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4_t, ob + 16 * LDS_ROW + dt * 32));
+          qT0[dt] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4_t, qb_ + dt * 32));
+          qT1[dt] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4_t, qb_ + 16 * LDS_ROW + dt * 32));
+        }
+      }
+      float pv[8], dsv[8];
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const float4 l2 = *reinterpret_cast<const float4*>(L2s + (2 * c + t) * 16 + 4 * fg);
+        const float4 dl = *reinterpret_cast<const float4*>(Dls + (2 * c + t) * 16 + 4 * fg);
+        const float l2a[4] = {l2.x, l2.y, l2.z, l2.w}, dla[4] = {dl.x, dl.y, dl.z, dl.w};
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float pr = key_ok ? __builtin_amdgcn_exp2f(fmaf(st[t][r], LOG2E, -l2a[r])) : 0.f;
+          pv[4 * t + r] = pr;
+          dsv[4 * t + r] = pr * (pt[t][r] - dla[r]);
+        }
+      }
+      const uint2 plo = pack4<P>(pv[0], pv[1], pv[2], pv[3]), phi = pack4<P>(pv[4], pv[5], pv[6], pv[7]);
+      const uint2 dlo = pack4<P>(dsv[0], dsv[1], dsv[2], dsv[3]), dhi = pack4<P>(dsv[4], dsv[5], dsv[6], dsv[7]);
+      const s16x8_t pf = __builtin_bit_cast(s16x8_t, make_uint4(plo.x, plo.y, phi.x, phi.y));
+      const s16x8_t df = __builtin_bit_cast(s16x8_t, make_uint4(dlo.x, dlo.y, dhi.x, dhi.y));
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) {
+        dv[dt] = P::mfma(__builtin_shufflevector(oT0[dt], oT1[dt], 0, 1, 2, 3, 4, 5, 6, 7), pf, dv[dt]);
+        dk[dt] = P::mfma(__builtin_shufflevector(qT0[dt], qT1[dt], 0, 1, 2, 3, 4, 5, 6, 7), df, dk[dt]);
+      }
+    }
+  }
+  if (active && key_ok) {
+    if (is_main) {
+      unsigned short* ok_ = p.dk + (row0 + key) * p.ld_dqkv + h * 64 + 4 * fg;
+      unsigned short* ov_ = p.dv + (row0 + key) * p.ld_dqkv + h * 64 + 4 * fg;
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) {
+        *reinterpret_cast<uint2*>(ok_ + dt * 16) = pack4<P>(dk[dt][0], dk[dt][1], dk[dt][2], dk[dt][3]);
+        *reinterpret_cast<uint2*>(ov_ + dt * 16) = pack4<P>(dv[dt][0], dv[dt][1], dv[dt][2], dv[dt][3]);
+      }
+    } else {
+      const long pr = (long)n * n_side + (key - p.n_kmain);
+      float* ok_ = p.dsk + pr * p.ld_dside + h * 64 + 4 * fg;
+      float* ov_ = p.dsv + pr * p.ld_dside + h * 64 + 4 * fg;
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) {
+        *reinterpret_cast<float4*>(ok_ + dt * 16) = make_float4(dk[dt][0], dk[dt][1], dk[dt][2], dk[dt][3]);
+        *reinterpret_cast<float4*>(ov_ + dt * 16) = make_float4(dv[dt][0], dv[dt][1], dv[dt][2], dv[dt][3]);
+      }
+    }
+  }
+}
+
+// GAVA_ATTN_STREAM=1 sends every non-causal shape to the streaming kernels (as in attention.hip)
+bool stream_forced() {
+  static const bool on = getenv("GAVA_ATTN_STREAM") && getenv("GAVA_ATTN_STREAM")[0] == '1';
+  return on;
+}
+
 template <class P, class PA, bool CAUSAL>
 int launch(const gava::AttnBwdMfmaParams& p, hipStream_t s) {
   dim3 grid(p.batch * p.heads), block(256);
   const int kt = (p.n_keys + 15) / 16, qt2 = ((p.n_q + 15) / 16 + 1) / 2 * 2;
-  if (kt <= 2) hipLaunchKernelGGL((attn_bwd_dq_kernel<P, PA, 2, CAUSAL>), grid, block, 0, s, p);
+  // the dQ kernel writes the row statistics the dK/dV kernel reads: both stream forms take the same statistics layout
+  const bool stream_q = !CAUSAL && (kt > 20 || stream_forced());
+  const bool stream_kv = !CAUSAL && (qt2 > 18 || stream_forced());
+  if (stream_q) hipLaunchKernelGGL((attn_bwd_dq_stream_kernel<P, PA>), dim3(p.batch * p.heads, ((p.n_q + 15) / 16 + 3) / 4), block, 0, s, p);
+  else if (kt <= 2) hipLaunchKernelGGL((attn_bwd_dq_kernel<P, PA, 2, CAUSAL>), grid, block, 0, s, p);
   else if (kt <= 6) hipLaunchKernelGGL((attn_bwd_dq_kernel<P, PA, 6, CAUSAL>), grid, block, 0, s, p);
   else if (kt <= 14) hipLaunchKernelGGL((attn_bwd_dq_kernel<P, PA, 14, CAUSAL>), grid, block, 0, s, p);
   else if (kt <= 20) hipLaunchKernelGGL((attn_bwd_dq_kernel<P, PA, 20, CAUSAL>), grid, block, 0, s, p);
   else return GAVA_EINVAL;
-  if (qt2 <= 2) hipLaunchKernelGGL((attn_bwd_dkv_kernel<P, PA, 2, CAUSAL>), grid, block, 0, s, p);
+  if (stream_kv) hipLaunchKernelGGL((attn_bwd_dkv_stream_kernel<P, PA>), dim3(p.batch * p.heads, (kt + 3) / 4), block, 0, s, p);
+  else if (qt2 <= 2) hipLaunchKernelGGL((attn_bwd_dkv_kernel<P, PA, 2, CAUSAL>), grid, block, 0, s, p);
   else if (qt2 <= 6) hipLaunchKernelGGL((attn_bwd_dkv_kernel<P, PA, 6, CAUSAL>), grid, block, 0, s, p);
   else if (qt2 <= 14) hipLaunchKernelGGL((attn_bwd_dkv_kernel<P, PA, 14, CAUSAL>), grid, block, 0, s, p);
   else if (qt2 <= 18) hipLaunchKernelGGL((attn_bwd_dkv_kernel<P, PA, 18, CAUSAL>), grid, block, 0, s, p);

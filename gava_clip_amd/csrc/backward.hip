@@ -171,7 +171,8 @@ extern "C" int gava_attention_backward(const gava_attention_bwd_args* a, gava_st
   p.n_g = a->n_g; p.T = n_side ? a->T : 1; p.has_summary = a->has_summary; p.n_keys = a->n + n_side;
   p.q_pad = ((p.n_q + 15) / 16 + 1) / 2 * 32;
   p.q_scale = a->q_scale;
-  if (p.n_keys > 320 || p.n_q > a->n || p.n_q > 288) return GAVA_EINVAL;
+  // longer key sets (> 320) and query sets (> 288) take the streaming kernels of attention_bwd.hip; the causal text form has none
+  if (p.n_q > a->n || (a->causal && (p.n_keys > 320 || p.n_q > 288))) return GAVA_EINVAL;
   return gava::attention_bwd_mfma(p, a->prec, a->act_prec_set ? a->act_prec : a->prec, a->causal, s);
 }
 

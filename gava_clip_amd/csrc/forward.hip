@@ -241,7 +241,6 @@ int check_vision(const gava_vision_model* m) {
   if (m->D > 1024) return GAVA_EINVAL;
   if (((long)m->B * m->T_in) % m->T_model) return GAVA_EINVAL;  // reference: view(B,T,C) fails (utils:160-163)
   const long g = m->size / m->P;
-  if (g * g + 1 + m->G + m->T_model + 1 > 320) return GAVA_EINVAL;
   return GAVA_OK;
 }
 

@@ -325,7 +325,7 @@ def layernorm(x, gamma, beta, *, out16=None, out32=None, prec, rows=None, in_str
 def attention(q, k, v, out, *, batch, heads, n_q, n_kmain, prec, causal=False,
               side_k=None, side_v=None, n_g=0, T=0, has_summary=False, split_out=False, q_batch_rows=0):
     a = AttentionArgs()
-    a.q, a.k, a.v, a.ld_qkv = ptr(q), ptr(k), ptr(v), q.stride(0)
+    a.q, a.k, a.v, a.ld_qkv = ptr(q), ptr(k), ptr(v), k.stride(0)   # q may be a separate buffer (q_batch_rows, ld_q)
     a.side_k, a.side_v = ptr(side_k), ptr(side_v)
     a.ld_side = side_k.stride(0) if side_k is not None else 0
     a.out, a.ld_out = ptr(out), out.stride(0)

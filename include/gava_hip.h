@@ -198,7 +198,7 @@ typedef struct {
 } gava_layernorm_args;
 int gava_layernorm(const gava_layernorm_args* a, gava_stream_t stream);
 
-/* Fused softmax(QK^T)V for head dim 64, whole key row resident in LDS (single-pass softmax).
+/* Fused softmax(QK^T)V for head dim 64, key rows resident in LDS or streamed (see below).
  * Replaces Attention.forward's einsum/softmax/einsum (VitaCLIP_vision_encoder_utils.py:71-77)
  * and the scaled-dot-product inside nn.MultiheadAttention (VitaCLIP_text_encoder.py:81-83).
  * Q must already carry the 1/sqrt(64) factor.  Problem (n, h): queries are rows
@@ -208,7 +208,8 @@ int gava_layernorm(const gava_layernorm_args* a, gava_stream_t stream);
  *   T   rows n_g + (n / T)*T + [0,T)            shared by the T frames of a clip (local prompts)
  *   1   row  n_g + batch + n                    per problem               (summary token)
  * With n_side == 0 there are no side rows.  causal: key j is visible to query i iff j <= i.
- * Total keys <= 320. */
+ * Up to 320 keys the key set is resident in LDS (single-pass softmax); longer non-causal key sets (long clips,
+ * 336/384 px inputs) take a key-streaming online-softmax kernel.  causal: at most 320 keys. */
 typedef struct {
   const void* q; const void* k; const void* v; int64_t ld_qkv;  /* h16, element strides */
   const void* side_k; const void* side_v; int64_t ld_side;
@@ -381,7 +382,8 @@ int gava_qgelu_backward(const void* pre, const void* dh, void* dpre, size_t n, i
 
 /* Softmax-attention backward (MFMA kernels).  q (already scaled by 1/sqrt(dh)), k, v, dout: h16 rows [batch*n][ld],
  * head h at columns [64h, 64h+64); writes dq (times q_scale, the factor folded into q), dk, dv as h16 rows
- * [batch*n][ld_dqkv].  n (+ prompt rows) <= 320.
+ * [batch*n][ld_dqkv].  Non-causal: any n; past 320 keys (n + prompt rows) or 288 query rows the dQ and dK/dV
+ * kernels stream the other side through LDS in blocks.  causal: n <= 288.
  *   - plain or causal sequences without prompt rows (side_k == NULL): the text tower (nn.MultiheadAttention at
  *     text_encoder.py:71,83) and the T-token summary attention (vision_encoder_utils.py:169-170);
  *   - vision blocks (vision_encoder_utils.py:190-191): keys = the n rows of the frame + the gathered prompt rows

@@ -405,6 +405,13 @@ if __name__ == "__main__":
         if "--c5-full" in sys.argv:
             run_case(mod, VIT_L14_T32, C3, 32, "c5_full", False, wseed=0, xseed=4244, compact=True)
         sys.exit(0)
+    if "--long" in sys.argv:         # shapes past 320 attention keys (key-streaming kernels): a long clip and a 320 px input
+        from gava_clip_amd.config import TINY_T320, TINY_320PX
+        run_case(mod, TINY_T320, C3, 2, "tiny_t320", False, compact=True)
+        run_case(mod, TINY_320PX, C3, 2, "tiny_320px", False, compact=True)
+        run_grad_case(mod, TINY_T320, C3, 2, "tiny_t320_grads", False)
+        run_grad_case(mod, TINY_320PX, C3, 2, "tiny_320px_grads", False)
+        sys.exit(0)
     if "--c2-full" in sys.argv:      # BASELINE config c2 at its full batch: 64 clips through the reference (logits + features only)
         run_case(mod, VIT_B16_T8, C3, 64, "c2_full", False, wseed=0, xseed=4242, compact=True)
         sys.exit(0)
