@@ -63,16 +63,27 @@ DeviceCtx& device_ctx() {
   return g_dev[d % MAX_DEVICES];
 }
 
-// CUs the persistent QKV GEMM leaves to the prompt-path kernels on the side stream.  Measured (tools/side_probe.py): with
-// 8 or 16 CUs left out a 128-workgroup kernel on the second stream still waits for the GEMM's first workgroups to retire
-// (0.23 ms instead of 0.01 ms) - workgroups are dealt round-robin to the XCDs' shader engines and the dispatch blocks on
-// the first engine without a free CU; with 32 (one CU per engine) it runs at its stand-alone speed and the GEMM is 4 % slower.
-// When LN1 runs before the QKV GEMM most of the prompt path finishes beside LN1 and only its tail waits: 8 is then the
-// better trade (23.85 vs 24.0 ms per forward); with LN1 folded away the whole path sits beside the GEMM: 32 (23.4 vs 23.75).
-int side_cus(bool ln1_folded) {
-  static const int forced = getenv("GAVA_SIDE_CUS") ? atoi(getenv("GAVA_SIDE_CUS")) : -1;
-  return forced >= 0 ? forced : (ln1_folded ? 32 : 8);
-}
+// The prompt path of block i runs on the side stream beside the main path's LN1 + QKV GEMM: fork(i) before it, done(i) after
+// it, join(i) on the caller's stream before the attention that reads its K/V rows.  Without a side stream (or with more than 64
+// blocks) all three are no-ops and the prompt path runs on the caller's stream.
+struct Side {
+  const SideStream& st; hipStream_t s; bool two;
+  Side(SideStream& side, hipStream_t s, int layers) : st(side), s(s), two(side.get() && layers <= 64) {}
+  gava_stream_t stream() const { return two ? (gava_stream_t)st.s : (gava_stream_t)s; }
+  int fork(int i) const {
+    return !two || (hipEventRecord(st.fork[i], s) == hipSuccess && hipStreamWaitEvent(st.s, st.fork[i], 0) == hipSuccess)
+               ? GAVA_OK : GAVA_ELAUNCH;
+  }
+  int done(int i) const { return !two || hipEventRecord(st.join[i], st.s) == hipSuccess ? GAVA_OK : GAVA_ELAUNCH; }
+  int join(int i) const { return !two || hipStreamWaitEvent(s, st.join[i], 0) == hipSuccess ? GAVA_OK : GAVA_ELAUNCH; }
+  // CUs the persistent QKV GEMM leaves to the prompt-path kernels on the side stream.  Measured (tools/side_probe.py): with
+  // 8 or 16 CUs left out a 128-workgroup kernel on the second stream still waits for the GEMM's first workgroups to retire
+  // (0.23 ms instead of 0.01 ms) - workgroups are dealt round-robin to the XCDs' shader engines and the dispatch blocks on
+  // the first engine without a free CU; with 32 (one CU per engine) it runs at its stand-alone speed and the GEMM is 4 % slower.
+  // When LN1 runs before the QKV GEMM most of the prompt path finishes beside LN1 and only its tail waits: 8 is then the
+  // better trade (23.85 vs 24.0 ms per forward); with LN1 folded away the whole path sits beside the GEMM: 32 (23.4 vs 23.75).
+  int cus(bool ln1_folded) const { return two ? (ln1_folded ? 32 : 8) : 0; }
+};
 
 struct Carver {
   char* base; size_t off, cap;
@@ -162,7 +173,7 @@ struct VisionWs {
 
 int patch_k(const gava_vision_model* m) { return (3 * m->P * m->P + 63) / 64 * 64; }
 
-// The A operand of the patch-embedding GEMM.
+// The A operand of the patch-embedding GEMM `a` (its shape already set).
 //   fp32 clips (the reference's input, the benchmark's), small batches: IM2COL-FREE - the GEMM builds its A tiles in the k-loop straight
 //   from the NCTHW frames (two coalesced float4 loads per 8 k-values, converted and written to the LDS stage: gemm_kernel's
 //   patch_load / patch_write); no patch matrix exists, one launch.  Big batches (enough 256 x 256 tiles for the persistent kernel,
@@ -171,26 +182,21 @@ int patch_k(const gava_vision_model* m) { return (3 * m->P * m->P + 63) / 64 * 6
 //   decoded uint8 videos (forward_frames): two passes - gava_patchify writes the 16-bit patch matrix once (0.46 ms: every
 //   element is a bilinear sample, 4 byte loads + the lerp), the GEMM stages it by LDS-DMA (0.26 ms).  Built inside the k-loop
 //   the same samples are recomputed for each of the three 256-column tiles and cannot hide behind 0.23 GF of MFMA work per
-//   frame: 2.33 ms.  GAVA_PATCH_DIRECT=0 / 1 forces the two-pass / the in-loop form for either source (A/B, op tests).
-int patch_operand(const gava_vision_model* m, const float* x, void* scratch, int Kp, int prec, gava_stream_t stream,
-                  gava_gemm_args* a) {
-  static const int forced = getenv("GAVA_PATCH_DIRECT") ? atoi(getenv("GAVA_PATCH_DIRECT")) : -1;
+//   frame: 2.33 ms.
+int patch_operand(const gava_vision_model* m, const float* x, void* scratch, gava_stream_t stream, gava_gemm_args* a) {
   // (P % 8 != 0 - ViT-L/14 - has no float4 form of the in-loop loader: eight scalar loads per chunk; it stays two-pass)
   // the in-loop loader reads the frames with float4 loads: a clip tensor whose storage is not 16-byte aligned (a view at an odd
   // offset) or whose rows are not a multiple of 4 floats takes the two-pass form, which has no such requirement
-  const bool aligned = m->clips != nullptr || ((((uintptr_t)x) & 15) == 0 && m->size % 4 == 0);
-  const long gp_ = m->size / m->P, rows = (long)m->B * m->T_in * gp_ * gp_;
-  const bool big = m->D % 256 == 0 && (rows + 255) / 256 * (m->D / 256) >= 512;      // gemm.hip's condition for the persistent kernel
-  const bool direct = forced >= 0 ? (forced != 0 && aligned) : (m->clips == nullptr && m->P % 8 == 0 && aligned && !big);
-  a->lda = Kp; a->frame_size = m->size; a->patch = m->P;
-  if (direct) {
-    a->A = nullptr; a->frames = m->clips ? nullptr : x; a->clips = m->clips; a->clip_lut = m->clip_lut;
+  const bool aligned = (((uintptr_t)x) & 15) == 0 && m->size % 4 == 0;
+  a->lda = a->K; a->frame_size = m->size; a->patch = m->P;
+  if (m->clips == nullptr && m->P % 8 == 0 && aligned && !gava::gemm_patch_on_persistent(a->M, a->N, a->lda, a->ldw)) {
+    a->A = nullptr; a->frames = x; a->clip_lut = m->clip_lut;
     return GAVA_OK;
   }
   gava_patchify_args pa{};
   pa.x = m->clips ? nullptr : x; pa.clips = m->clips; pa.clip_lut = m->clip_lut;
-  pa.B = m->B; pa.T = m->T_in; pa.size = m->size; pa.patch = m->P; pa.prec = prec;
-  pa.out = scratch; pa.ldo = Kp;
+  pa.B = m->B; pa.T = m->T_in; pa.size = m->size; pa.patch = m->P; pa.prec = a->prec;
+  pa.out = scratch; pa.ldo = a->K;
   a->A = scratch;
   return gava_patchify(&pa, stream);
 }
@@ -240,19 +246,148 @@ int check_vision(const gava_vision_model* m) {
   if (m->size % m->P || m->D != m->H * 64 || m->D % 128 || m->F % 128 || m->E % 128) return GAVA_EINVAL;
   if (m->D > 1024) return GAVA_EINVAL;
   if (((long)m->B * m->T_in) % m->T_model) return GAVA_EINVAL;  // reference: view(B,T,C) fails (utils:160-163)
-  const long g = m->size / m->P;
   return GAVA_OK;
 }
+
+// Big batches fold LayerNorm with pre-reduced row sums (FoldPlan)
+bool fused_stats(long R, int D) { return R >= 8192 && D % 256 == 0 && D <= 1024 && D >= 256; }
 
 // does the inference driver keep the residual stream as a 16-bit pair for this model and batch? (see `pair` in the driver)
 bool pair_stream(const gava_vision_model* m) {
   const long g = m->size / m->P, R = (long)m->B * m->T_in * (g * g + 1);
   const int D = m->D, F = m->F, WL = m->w_lo ? 2 : 1;
-  bool pair = m->w_lo != 2 && m->layers >= 2 && R >= 8192 && D % 256 == 0 && D >= 256 &&
-              !(getenv("GAVA_FUSED_STATS") && getenv("GAVA_FUSED_STATS")[0] == '0') && !getenv("GAVA_NO_PREFUSE") && !getenv("GAVA_NO_LASTFOLD") &&
+  bool pair = m->w_lo != 2 && m->layers >= 2 && fused_stats(R, D) &&
               gava::gemm_takes_pair((int)R, D, D, D, (long)WL * D) && gava::gemm_takes_pair((int)R, D, F, F, (long)WL * F);
   for (int i = 0; pair && i + 1 < m->layers; ++i) pair = m->layer[i].w_fc1_fold && m->layer[i + 1].w_qkv_fold;
   return pair;
+}
+
+// ---- the stages both vision drivers run (gava_vision_forward_train, gava_vision_forward_keep)
+
+struct VisionShape {
+  int n, BT, R, D, F, E, H, G, Tm, pr, Kp, SR;
+  long fs;   // frame stride in X
+  explicit VisionShape(const gava_vision_model* m)
+      : n((m->size / m->P) * (m->size / m->P)), BT(m->B * m->T_in), R(BT * (n + 1)), D(m->D), F(m->F), E(m->E), H(m->H),
+        G(m->G), Tm(m->T_model), pr(m->prec), Kp(patch_k(m)), SR(G + 2 * BT), fs((long)(n + 1) * D) {}
+};
+
+// check the model and the arguments both drivers take, carve the workspace
+int open_vision(const gava_vision_model* m, const float* x, const float* cls_x, const float* summary, void* workspace,
+                size_t workspace_bytes, VisionWs* w) {
+  TRY(check_vision(m));
+  if ((!x && !m->clips) || !cls_x || !summary || !workspace) return GAVA_EINVAL;
+  *w = carve_vision(m, workspace, workspace_bytes);
+  return w->total > workspace_bytes ? GAVA_EWORKSPACE : GAVA_OK;
+}
+
+// embedding (VitaCLIP_vision_encoder.py:105-113) into the fp32 stream `out`: patch GEMM + bias, pos and time embedding, CLS rows.
+// Im2col-free for fp32 clips, patch matrix (parked in `scratch`) + LDS-DMA GEMM otherwise: see patch_operand
+int embed(const gava_vision_model* m, const VisionShape& v, const float* x, int wl, float* out, void* scratch,
+          gava_stream_t stream) {
+  gava_gemm_args a{};
+  a.W = m->w_patch; a.ldw = (wl ? 2 : 1) * v.Kp; a.bias = m->b_patch; a.w_lo = wl;
+  a.out = out; a.ldo = v.D; a.M = v.BT * v.n; a.N = v.D; a.K = v.Kp; a.epilogue = GAVA_EPI_F32_PATCH; a.prec = v.pr;
+  a.pos = m->pos_embed; a.time = m->time_embed; a.n_patches = v.n; a.T = m->T_in;
+  TRY(patch_operand(m, x, scratch, stream, &a));
+  TRY(gava_gemm(&a, stream));
+  return gava::cls_embed(out, m->cls_token, m->pos_embed, m->time_embed, v.BT, m->T_in, v.D, v.fs, (hipStream_t)stream);
+}
+
+// prompt ("side") path of one block: cls_proj, summary token, local prompts -> the K/V-only rows `skv` (SR rows).  cls_proj's
+// operand is h16 of the CLS rows of the fp32 stream X - or, when `hi` is given, their 16-bit copy already there (the pair
+// stream's hi half, frames fs apart)
+int prompt_path(const VisionShape& v, const gava_vision_layer& L, int wl, const VisionWs& w, const float* X, const void* hi,
+                void* skv, gava_stream_t ss) {
+  const int D = v.D, BT = v.BT, pr = v.pr;
+  if (hi) {
+    TRY(gemm_x(wl, hi, v.fs, L.w_cls, D, L.b_cls, w.CP, D, BT, D, D, GAVA_EPI_F32, pr, ss));
+  } else {
+    TRY(ln(X, v.fs, nullptr, nullptr, nullptr, w.CLS16, D, nullptr, 0, BT, D, pr, ss));
+    TRY(gemm_x(wl, w.CLS16, D, L.w_cls, D, L.b_cls, w.CP, D, BT, D, D, GAVA_EPI_F32, pr, ss));
+  }
+  TRY(ln(w.CP, D, nullptr, L.sln_g, L.sln_b, w.CPn, D, nullptr, 0, BT, D, pr, ss));
+  TRY(gemm_x(wl, w.CPn, D, L.w_sqkv, D, L.b_sqkv, w.SQKV, 3 * D, BT, 3 * D, D, GAVA_EPI_H16, pr, ss, nullptr, 0, D, 0.125f));
+  {
+    gava_attention_args a{};
+    const unsigned short* q = (const unsigned short*)w.SQKV;
+    a.q = q; a.k = q + D; a.v = q + 2 * D; a.ld_qkv = 3 * D; a.out = w.SMIX; a.ld_out = D;
+    a.batch = BT / v.Tm; a.heads = v.H; a.n_q = v.Tm; a.n_kmain = v.Tm; a.prec = pr;
+    TRY(gava_attention(&a, ss));
+  }
+  TRY(gemm_x(wl, w.SMIX, D, L.w_sout, D, L.b_sout, w.SUMM, D, BT, D, D, GAVA_EPI_F32, pr, ss, w.CP, D));
+  TRY(gava::side_ln(L.global_prompts, L.local_prompts, w.CP, w.SUMM, L.ln1_g, L.ln1_b, w.SIDEn, v.G, v.Tm, BT, D, pr, (hipStream_t)ss));
+  const unsigned short* wkv = (const unsigned short*)L.w_qkv + (long)D * (wl ? 2 : 1) * D;
+  return gemm_x(wl, w.SIDEn, D, wkv, D, L.b_qkv + D, skv, 2 * D, v.SR, 2 * D, D, GAVA_EPI_H16, pr, ss);
+}
+
+// LayerNorm folding: the producing GEMM (out_proj / fc2 of the block before) leaves a 16-bit copy of x in Xn plus row-sum
+// partials, the consuming GEMM (fc1 / qkv) applies the normalisation in its epilogue.  Big batches (fused_stats): the producers
+// pre-reduce their row sums per 256-column tile and the consumers turn them into (mean, rstd) themselves - no gava_row_stats
+// launch between producer and consumer (each cost ~33 us of forward time for a 9 us kernel: two kernel boundaries behind a
+// persistent GEMM).
+struct FoldPlan {
+  const VisionWs& w; int R, D; bool fused;
+  FoldPlan(const VisionWs& w, int R, int D) : w(w), R(R), D(D), fused(fused_stats(R, D)) {}
+  Fold produce() const {
+    Fold p; p.x16 = w.Xn; p.ld_x16 = D; p.rowsum = w.RSUM; p.reduced = fused ? 1 : 0;
+    return p;
+  }
+  Fold consume(const float* s, const float* t) const {
+    Fold c; c.s = s; c.t = t;
+    if (fused) c.partials = w.RSUM; else c.stats = w.STATS;
+    return c;
+  }
+  int stats(gava_stream_t stream) const { return fused ? GAVA_OK : gava_row_stats(w.RSUM, D / 64, D, R, w.STATS, stream); }
+};
+
+// the QKV GEMM over every row of Xn into qkv, or with kv_only its K/V columns alone (the last block, whose queries are made for
+// the CLS rows only).  fold_s != nullptr: norm1 is folded into it (Xn holds the 16-bit copy of the un-normalised stream)
+int qkv_gemm(const VisionShape& v, const gava_vision_layer& L, int wl, bool kv_only, const FoldPlan& fp, const float* fold_s,
+             const Lo8* lo, unsigned short* qkv, int resv, gava_stream_t stream) {
+  const int D = v.D, c0 = kv_only ? D : 0;   // first output column
+  const unsigned short* W = (const unsigned short*)(fold_s ? L.w_qkv_fold : L.w_qkv) + (long)c0 * (wl ? 2 : 1) * D;
+  const Fold c = fold_s ? fp.consume(fold_s + c0, L.qkv_fold_t + c0) : Fold{};
+  return gemm_x(wl, fp.w.Xn, D, W, D, fold_s ? nullptr : L.b_qkv + c0, qkv + c0, 3 * D, v.R, 3 * D - c0, D, GAVA_EPI_H16, v.pr,
+                stream, nullptr, 0, kv_only ? 0 : D, kv_only ? 1.f : 0.125f, 0, nullptr, fold_s ? &c : nullptr, resv, lo);
+}
+
+// the last block's B*T CLS queries, from the CLS rows of the stream X: with norm1 folded into the K/V GEMM they get a LayerNorm
+// of their own, else they are rows of Xn
+int cls_queries(const VisionShape& v, const gava_vision_layer& L, int wl, bool fold1, const float* X, const VisionWs& w, void* qc,
+                gava_stream_t stream) {
+  const int D = v.D;
+  if (fold1) TRY(ln(X, v.fs, nullptr, L.ln1_g, L.ln1_b, w.XNC, D, nullptr, 0, v.BT, D, v.pr, stream));
+  return gemm_x(wl, fold1 ? w.XNC : w.Xn, fold1 ? D : v.fs, L.w_qkv, D, L.b_qkv, qc, D, v.BT, D, D, GAVA_EPI_H16, v.pr, stream,
+                nullptr, 0, D, 0.125f);
+}
+
+// attention of every frame's tokens over its own keys + the prompt K/V rows skv; with q != nullptr the CLS query of each
+// frame only (rows D apart; the last block), its output split_out-packed
+int frame_attention(const VisionShape& v, const unsigned short* qkv, const void* q, const void* skv, void* out, long ld_out,
+                    int split_out, gava_stream_t stream) {
+  const int D = v.D;
+  const unsigned short* sk = (const unsigned short*)skv;
+  gava_attention_args a{};
+  a.q = q ? q : qkv;
+  if (q) { a.ld_q = D; a.q_batch_rows = 1; }
+  a.k = qkv + D; a.v = qkv + 2 * D; a.ld_qkv = 3 * D;
+  a.side_k = sk; a.side_v = sk + D; a.ld_side = 2 * D;
+  a.out = out; a.ld_out = ld_out; a.split_out = split_out;
+  a.batch = v.BT; a.heads = v.H; a.n_q = q ? 1 : v.n + 1; a.n_kmain = v.n + 1;
+  a.n_g = v.G; a.T = v.Tm; a.has_summary = 1; a.prec = v.pr;
+  return gava_attention(&a, stream);
+}
+
+// head (VitaCLIP_vision_encoder.py:126-130) on the CLS rows of the final stream X.  Split precision (3 MFMA passes): M = BT
+// rows only, and its rounding lands directly on the output
+int head(const gava_vision_model* m, const VisionShape& v, const float* X, const VisionWs& w, float* cls_x, float* summary,
+         gava_stream_t stream) {
+  const int D = v.D, E = v.E, pr = v.pr;
+  TRY(ln(X, v.fs, nullptr, m->lnpost_g, m->lnpost_b, w.CLSPOST, 3 * D, nullptr, 0, v.BT, D, pr, stream, 1));
+  TRY(gemm(w.CLSPOST, 3 * D, m->w_proj, 3 * D, nullptr, w.PROJ, E, v.BT, E, 3 * D, GAVA_EPI_F32, pr, stream));
+  TRY(gava::mean_rows(w.PROJ, cls_x, m->B, m->T_in, E, (hipStream_t)stream));
+  return gava::mean_rows(w.SUMM, summary, v.BT / v.Tm, v.Tm, D, (hipStream_t)stream);
 }
 
 }  // namespace
@@ -309,37 +444,22 @@ extern "C" int gava_vision_forward(const gava_vision_model* m, const float* x, f
 extern "C" int gava_vision_forward_train(const gava_vision_model* m, const float* x, float* cls_x, float* summary,
                                          float* debug_cls, float* saved_x, void* workspace, size_t workspace_bytes,
                                          gava_stream_t stream) {
-  TRY(check_vision(m));
-  if ((!x && !m->clips) || !cls_x || !summary || !workspace) return GAVA_EINVAL;
-  const VisionWs w = carve_vision(m, workspace, workspace_bytes);
-  if (w.total > workspace_bytes) return GAVA_EWORKSPACE;
+  VisionWs w;
+  TRY(open_vision(m, x, cls_x, summary, workspace, workspace_bytes, &w));
+  // weight-lo pass (gava_vision_model.w_lo): every weight below except the *_split ones is [W_hi | W_lo], 2x the columns
+  const int wl = m->w_lo ? 1 : 0;
+  if (wl && saved_x) return GAVA_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   DeviceCtx& dc = device_ctx();
   std::lock_guard<std::mutex> lock(dc.mu);
-  SideStream& g_side = dc.side;
   Fc1Probe& g_probe = dc.probe;
-  const int g = m->size / m->P, n = g * g, BT = m->B * m->T_in, R = BT * (n + 1);
-  const int D = m->D, F = m->F, E = m->E, G = m->G, Tm = m->T_model, pr = m->prec;
-  const int Kp = patch_k(m), SR = G + 2 * BT;
-  const long fs = (long)(n + 1) * D;  // frame stride in X
-  // weight-lo pass (gava_vision_model.w_lo): every weight below except the *_split ones is [W_hi | W_lo], 2x the columns
-  const int wl = m->w_lo ? 1 : 0, WL = wl ? 2 : 1;
-  if (wl && saved_x) return GAVA_EINVAL;
+  const VisionShape v(m);
+  const int BT = v.BT, R = v.R, D = v.D, F = v.F, pr = v.pr;
+  const long fs = v.fs;
   // w_lo = 2: the LayerNorm-folded qkv / fc1 GEMMs and fc2 run their lo product at 8 bits (shapes the persistent kernel takes)
   const bool l8 = m->w_lo == 2 && m->layer8 && pr == GAVA_PREC_F16 && D % 256 == 0 && F % 256 == 0;
-  const char* h16 = nullptr; (void)h16;
 
-  // ---- embedding (VitaCLIP_vision_encoder.py:105-113)
-  {
-    // im2col-free for fp32 clips, patch matrix + LDS-DMA GEMM for decoded uint8 videos: see patch_operand
-    gava_gemm_args a{};
-    TRY(patch_operand(m, x, w.HID, Kp, pr, stream, &a));
-    a.W = m->w_patch; a.ldw = WL * Kp; a.bias = m->b_patch; a.w_lo = wl;
-    a.out = w.X; a.ldo = D; a.M = BT * n; a.N = D; a.K = Kp; a.epilogue = GAVA_EPI_F32_PATCH; a.prec = pr;
-    a.pos = m->pos_embed; a.time = m->time_embed; a.n_patches = n; a.T = m->T_in;
-    TRY(gava_gemm(&a, stream));
-  }
-  TRY(gava::cls_embed(w.X, m->cls_token, m->pos_embed, m->time_embed, BT, m->T_in, D, fs, s));
+  TRY(embed(m, v, x, wl, w.X, w.HID, stream));
   // training: slot 0 = the embedding before ln_pre, slot 1+i = the input of block i, slot layers+1 = the final stream
   auto keep = [&](int slot) -> int {
     if (!saved_x) return GAVA_OK;
@@ -347,9 +467,6 @@ extern "C" int gava_vision_forward_train(const gava_vision_model* m, const float
                ? GAVA_OK : GAVA_ELAUNCH;
   };
   TRY(keep(0));
-  // ln_pre, and in the same row pass norm1 of block 0 (both read the same rows: one read of the embedding instead of two)
-  static const bool no_prefuse = getenv("GAVA_NO_PREFUSE") != nullptr;     // A/B switches (tools/ab_env.py)
-  static const bool no_lastfold = getenv("GAVA_NO_LASTFOLD") != nullptr;
   // timing diagnostics (results are WRONG): how much of a kernel's duration the forward gives back when it is removed.
   // Compiled in only by experiment builds (tools/ab_build.sh NAME -DGAVA_ENABLE_ABLATE), never into the product library.
 #ifdef GAVA_ENABLE_ABLATE
@@ -357,16 +474,15 @@ extern "C" int gava_vision_forward_train(const gava_vision_model* m, const float
 #else
   constexpr bool skip_attn = false, skip_stats = false;
 #endif
-  const bool pre_fused = m->layers >= 1 && !no_prefuse;
   // The residual stream as a 16-bit pair (inference, big batches, every block's LayerNorms folded): between ln_pre and the last
   // block the stream exists only as hi = h16(x) - which IS the operand of the GEMM consuming the fold (Xn) - and lo = fp16(x - hi)
   // (Xlo); out_proj / fc2 read and write the pair (8 bytes per element through their epilogue instead of 10).  Block 0's operand
   // is the NORMALISED stream (norm1 is fused into ln_pre's pass), so its hi half parks in HID until fc1 overwrites that; the last
   // block works on fp32 CLS rows again (join_rows).  |x - hi - lo| <= 2^-22 |x|.  GAVA_PAIR_STREAM=0: the fp32 stream (A/B).
-  const bool pair = !saved_x && pre_fused && !no_lastfold && pair_stream(m);
-  if (pre_fused) TRY(ln(w.X, D, nullptr, m->lnpre_g, m->lnpre_b, w.Xn, D, pair ? nullptr : w.X, D, R, D, pr, stream, 0, m->layer[0].ln1_g, m->layer[0].ln1_b,
-                        pair ? w.HID : nullptr, pair ? w.Xlo : nullptr, D));
-  else TRY(ln(w.X, D, nullptr, m->lnpre_g, m->lnpre_b, nullptr, 0, w.X, D, R, D, pr, stream));
+  const bool pair = !saved_x && pair_stream(m);
+  // ln_pre, and in the same row pass norm1 of block 0 (both read the same rows: one read of the embedding instead of two)
+  TRY(ln(w.X, D, nullptr, m->lnpre_g, m->lnpre_b, w.Xn, D, pair ? nullptr : w.X, D, R, D, pr, stream, 0, m->layer[0].ln1_g, m->layer[0].ln1_b,
+         pair ? w.HID : nullptr, pair ? w.Xlo : nullptr, D));
 
   // ---- blocks (VitaCLIP_vision_encoder.py:115-121, VitaCLIP_vision_encoder_utils.py:155-203)
   bool folded_in = false;   // Xn / STATS already hold this block's un-normalised input and its row statistics
@@ -379,87 +495,39 @@ extern "C" int gava_vision_forward_train(const gava_vision_model* m, const float
     if (k == 1) { g_probe.n = i + 1; g_probe.valid |= 1ull << i; }
     return GAVA_OK;
   };
-  auto not_last_blk = [&](int i) { return i + 1 < m->layers; };
+  const Side side(dc.side, s, m->layers);
+  const FoldPlan fp(w, R, D);
+  Fold produce = fp.produce();
+  if (pair) { produce.rlo = w.Xlo; produce.xlo = w.Xlo; }
   for (int i = 0; i < m->layers; ++i) {
     const gava_vision_layer& L = m->layer[i];
     TRY(keep(1 + i));
-    const unsigned short* wqkv = (const unsigned short*)L.w_qkv;
-    // prompt ("side") path: cls_proj, summary token, local prompts -> K/V-only rows.  The main path does not
-    // need it before attention, so it runs on the side stream next to LN1 + the QKV GEMM.
-    const bool two = g_side.get() && m->layers <= 64;
-    gava_stream_t ss = two ? (gava_stream_t)g_side.s : stream;
-    if (two) {
-      if (hipEventRecord(g_side.fork[i], s) != hipSuccess || hipStreamWaitEvent(g_side.s, g_side.fork[i], 0) != hipSuccess)
-        return GAVA_ELAUNCH;
-    }
+    // the prompt path: the main path does not need it before attention
+    TRY(side.fork(i));
     // the CLS rows as cls_proj's operand: h16 of the stream - with the pair, its hi half where it lies
     const void* hi_in = i == 0 ? w.HID : w.Xn;
-    if (pair) {
-      TRY(gemm_x(wl, hi_in, fs, L.w_cls, D, L.b_cls, w.CP, D, BT, D, D, GAVA_EPI_F32, pr, ss));
-    } else {
-      TRY(ln(w.X, fs, nullptr, nullptr, nullptr, w.CLS16, D, nullptr, 0, BT, D, pr, ss));
-      TRY(gemm_x(wl, w.CLS16, D, L.w_cls, D, L.b_cls, w.CP, D, BT, D, D, GAVA_EPI_F32, pr, ss));
-    }
-    TRY(ln(w.CP, D, nullptr, L.sln_g, L.sln_b, w.CPn, D, nullptr, 0, BT, D, pr, ss));
-    TRY(gemm_x(wl, w.CPn, D, L.w_sqkv, D, L.b_sqkv, w.SQKV, 3 * D, BT, 3 * D, D, GAVA_EPI_H16, pr, ss, nullptr, 0, D, 0.125f));
-    {
-      gava_attention_args a{};
-      const unsigned short* q = (const unsigned short*)w.SQKV;
-      a.q = q; a.k = q + D; a.v = q + 2 * D; a.ld_qkv = 3 * D; a.out = w.SMIX; a.ld_out = D;
-      a.batch = BT / Tm; a.heads = m->H; a.n_q = Tm; a.n_kmain = Tm; a.prec = pr;
-      TRY(gava_attention(&a, ss));
-    }
-    TRY(gemm_x(wl, w.SMIX, D, L.w_sout, D, L.b_sout, w.SUMM, D, BT, D, D, GAVA_EPI_F32, pr, ss, w.CP, D));
-    TRY(gava::side_ln(L.global_prompts, L.local_prompts, w.CP, w.SUMM, L.ln1_g, L.ln1_b, w.SIDEn, G, Tm, BT, D, pr, (hipStream_t)ss));
-    TRY(gemm_x(wl, w.SIDEn, D, wqkv + (long)D * WL * D, D, L.b_qkv + D, w.SIDEKV, 2 * D, SR, 2 * D, D, GAVA_EPI_H16, pr, ss));
-    if (two && hipEventRecord(g_side.join[i], g_side.s) != hipSuccess) return GAVA_ELAUNCH;
-    const int resv = two ? side_cus(folded_in) : 0;   // the persistent QKV GEMM leaves side_cus() CUs to the side kernels
-    // main path.  LayerNorm folding (inference only, when the model carries the folded weights): norm2 of every block
-    // but the last and norm1 of blocks 1..layers-2 are not launched; the producing GEMM (out_proj / fc2 of the block
-    // before) leaves a 16-bit copy of x in Xn plus row-sum partials, gava_row_stats makes (mean, rstd) of them and the
-    // consuming GEMM (fc1 / qkv) applies the normalisation in its epilogue.
+    TRY(prompt_path(v, L, wl, w, w.X, pair ? hi_in : nullptr, w.SIDEKV, side.stream()));
+    TRY(side.done(i));
+    const int resv = side.cus(folded_in);   // the persistent QKV GEMM leaves these CUs to the side kernels
+    // main path.  LayerNorm folding (inference only, when the model carries the folded weights; FoldPlan): norm2 of every block
+    // but the last and norm1 of blocks 1..layers-1 are not launched.
     const bool not_last = i + 1 < m->layers;
     const bool fold2 = !saved_x && not_last && L.w_fc1_fold && D % 64 == 0;
     const bool fold1 = folded_in;                                                    // set by the previous block's fc2
     // (the last block consumes the fold too: its K/V GEMM over all rows; its CLS queries get a LayerNorm of their own)
-    const bool fold1_next = !saved_x && i + (no_lastfold ? 2 : 1) < m->layers && m->layer[i + 1].w_qkv_fold && D % 64 == 0;
-    // big batches: the producers pre-reduce their row sums per 256-column tile and the consumers turn them into
-    // (mean, rstd) themselves - no gava_row_stats launch between producer and consumer (each cost ~33 us of forward time
-    // for a 9 us kernel: two kernel boundaries behind a persistent GEMM).  GAVA_FUSED_STATS=0: the launch stays (A/B).
-    static const bool fused_env = !(getenv("GAVA_FUSED_STATS") && getenv("GAVA_FUSED_STATS")[0] == '0');
-    const bool fused = fused_env && R >= 8192 && D % 256 == 0 && D <= 1024 && D >= 256;
-    Fold produce; produce.x16 = w.Xn; produce.ld_x16 = D; produce.rowsum = w.RSUM; produce.reduced = fused ? 1 : 0;
-    if (pair) { produce.rlo = w.Xlo; produce.xlo = w.Xlo; }
-    auto consume = [&](const float* s_, const float* t_) {
-      Fold c; c.s = s_; c.t = t_;
-      if (fused) c.partials = w.RSUM; else c.stats = w.STATS;
-      return c;
-    };
-    if (!fold1 && !(i == 0 && pre_fused)) TRY(ln(w.X, D, nullptr, L.ln1_g, L.ln1_b, w.Xn, D, nullptr, 0, R, D, pr, stream));
-    const unsigned short* sk = (const unsigned short*)w.SIDEKV;
+    const bool fold1_next = !saved_x && not_last && m->layer[i + 1].w_qkv_fold && D % 64 == 0;
+    if (!fold1 && i > 0) TRY(ln(w.X, D, nullptr, L.ln1_g, L.ln1_b, w.Xn, D, nullptr, 0, R, D, pr, stream));
     const gava_vision_layer8* L8 = l8 ? &m->layer8[i] : nullptr;
+    const float* qkv_s = fold1 ? (L8 ? L8->qkv_fold_s8 : L.qkv_fold_s) : nullptr;
     if (not_last) {
+      Lo8 lq; if (L8) { lq.A8 = w.Xn8; lq.W8 = L8->w_qkv_fold8; lq.exp = L8->qkv_fold_exp; }
       if (fold1) TRY(mark(GAVA_PROBE_QKV, i, 0));     // the folded form only: the instantiation bench.py's table names
-      if (fold1) {
-        Fold c = consume(L8 ? L8->qkv_fold_s8 : L.qkv_fold_s, L.qkv_fold_t);
-        Lo8 lo; if (L8) { lo.A8 = w.Xn8; lo.W8 = L8->w_qkv_fold8; lo.exp = L8->qkv_fold_exp; }
-        TRY(gemm_x(wl, w.Xn, D, L.w_qkv_fold, D, nullptr, w.QKV, 3 * D, R, 3 * D, D, GAVA_EPI_H16, pr, stream, nullptr, 0, D, 0.125f, 0, nullptr, &c, resv, L8 ? &lo : nullptr));
-      } else
-      TRY(gemm_x(wl, w.Xn, D, L.w_qkv, D, L.b_qkv, w.QKV, 3 * D, R, 3 * D, D, GAVA_EPI_H16, pr, stream, nullptr, 0, D, 0.125f, 0, nullptr, nullptr, resv));
+      TRY(qkv_gemm(v, L, wl, false, fp, qkv_s, fold1 && L8 ? &lq : nullptr, (unsigned short*)w.QKV, resv, stream));
       if (fold1) TRY(mark(GAVA_PROBE_QKV, i, 1));
-      if (two && hipStreamWaitEvent(s, g_side.join[i], 0) != hipSuccess) return GAVA_ELAUNCH;
-      {
-        gava_attention_args a{};
-        const unsigned short* q = (const unsigned short*)w.QKV;
-        a.q = q; a.k = q + D; a.v = q + 2 * D; a.ld_qkv = 3 * D;
-        a.side_k = sk; a.side_v = sk + D; a.ld_side = 2 * D;
-        a.out = w.MIX; a.ld_out = D;
-        a.batch = BT; a.heads = m->H; a.n_q = n + 1; a.n_kmain = n + 1;
-        a.n_g = G; a.T = Tm; a.has_summary = 1; a.prec = pr;
-        TRY(mark(GAVA_PROBE_ATTN, i, 0));
-        if (!skip_attn) TRY(gava_attention(&a, stream));
-        TRY(mark(GAVA_PROBE_ATTN, i, 1));
-      }
+      TRY(side.join(i));
+      TRY(mark(GAVA_PROBE_ATTN, i, 0));
+      if (!skip_attn) TRY(frame_attention(v, (const unsigned short*)w.QKV, nullptr, w.SIDEKV, w.MIX, D, 0, stream));
+      TRY(mark(GAVA_PROBE_ATTN, i, 1));
       TRY(mark(GAVA_PROBE_OUT, i, 0));
       if (fold2) {
         Lo8 po; if (L8) { po.x8 = w.Xn8; po.ldx8 = 2 * D; }      // out_proj: 16-bit lo product, bf8 copy of x16 for fc1
@@ -469,8 +537,8 @@ extern "C" int gava_vision_forward_train(const gava_vision_model* m, const float
         } else
         TRY(gemm_x(wl, w.MIX, D, L.w_out, D, L.b_out, w.X, D, R, D, D, GAVA_EPI_F32, pr, stream, w.X, D, 0, 1.f, 0, nullptr, &produce, 0, L8 ? &po : nullptr));
         TRY(mark(GAVA_PROBE_OUT, i, 1));
-        if (!skip_stats && !fused) TRY(gava_row_stats(w.RSUM, D / 64, D, R, w.STATS, stream));
-        Fold c = consume(L8 ? L8->fc1_fold_s8 : L.fc1_fold_s, L.fc1_fold_t);
+        if (!skip_stats) TRY(fp.stats(stream));
+        Fold c = fp.consume(L8 ? L8->fc1_fold_s8 : L.fc1_fold_s, L.fc1_fold_t);
         Lo8 lo; if (L8) { lo.A8 = w.Xn8; lo.W8 = L8->w_fc1_fold8; lo.exp = L8->fc1_fold_exp; lo.out8 = w.HID8; lo.ldo8 = 2 * F; }
         TRY(mark(GAVA_PROBE_FC1, i, 0));
         TRY(gemm_x(wl, w.Xn, D, L.w_fc1_fold, D, nullptr, w.HID, F, R, F, D, GAVA_EPI_H16_QGELU, pr, stream, nullptr, 0, 0, 1.f, 0, nullptr, &c, 0, L8 ? &lo : nullptr));
@@ -495,7 +563,7 @@ extern "C" int gava_vision_forward_train(const gava_vision_model* m, const float
         } else
         TRY(gemm_x(wl, w.HID, F, L.w_fc2, F, L.b_fc2, w.X, D, R, D, F, GAVA_EPI_F32, pr, stream, w.X, D, 0, 1.f, 0, nullptr, &produce, 0, L8 ? &f2 : nullptr));
         TRY(mark(GAVA_PROBE_FC2, i, 1));
-        if (!skip_stats && !fused) TRY(gava_row_stats(w.RSUM, D / 64, D, R, w.STATS, stream));
+        if (!skip_stats) TRY(fp.stats(stream));
       } else {
         TRY(gemm_x(wl, w.HID, F, L.w_fc2, F, L.b_fc2, w.X, D, R, D, F, GAVA_EPI_F32, pr, stream, w.X, D, 0, 1.f, 0, nullptr, nullptr, 0, f2_8 ? &f2 : nullptr));
         TRY(mark(GAVA_PROBE_FC2, i, 1));
@@ -507,57 +575,32 @@ extern "C" int gava_vision_forward_train(const gava_vision_model* m, const float
       // needed for every token, queries / out_proj / MLP only for the B*T CLS rows: same results,
       // 1/197 of the row work.
       if (pair) TRY(gava::join_rows(w.Xn, w.Xlo, fs, w.X, fs, BT, D, pr, s));      // those rows as fp32 again
-      if (fold1) {   // norm1 folded into the K/V GEMM: Xn holds the 16-bit copy of the un-normalised stream
-        Fold c = consume((L8 ? L8->qkv_fold_s8 : L.qkv_fold_s) + D, L.qkv_fold_t + D);
-        Lo8 lo; if (L8) { lo.A8 = w.Xn8; lo.W8 = (const char*)L8->w_qkv_fold8 + (size_t)D * 4 * D; lo.exp = L8->qkv_fold_exp; }
-        TRY(gemm_x(wl, w.Xn, D, (const unsigned short*)L.w_qkv_fold + (long)D * WL * D, D, nullptr, (unsigned short*)w.QKV + D, 3 * D, R, 2 * D, D,
-                 GAVA_EPI_H16, pr, stream, nullptr, 0, 0, 1.f, 0, nullptr, &c, resv, L8 ? &lo : nullptr));
-      } else {
-        TRY(gemm_x(wl, w.Xn, D, wqkv + (long)D * WL * D, D, L.b_qkv + D, (unsigned short*)w.QKV + D, 3 * D, R, 2 * D, D, GAVA_EPI_H16, pr, stream, nullptr, 0, 0, 1.f, 0, nullptr, nullptr, resv));
-      }
+      Lo8 lo; if (L8) { lo.A8 = w.Xn8; lo.W8 = (const char*)L8->w_qkv_fold8 + (size_t)D * 4 * D; lo.exp = L8->qkv_fold_exp; }
+      TRY(qkv_gemm(v, L, wl, true, fp, qkv_s, fold1 && L8 ? &lo : nullptr, (unsigned short*)w.QKV, resv, stream));
       // split precision for these B*T rows when the model carries the split-packed weights (gava_vision_layer)
       const int sp = (!saved_x && L.w_q_split && L.w_out_split && L.w_fc1_split && L.w_fc2_split) ? 1 : 0;
       const int S = sp ? 3 : 1;
       if (sp) {
         TRY(ln(w.X, fs, nullptr, L.ln1_g, L.ln1_b, w.XNC, 3 * D, nullptr, 0, BT, D, pr, stream, 1));
         TRY(gemm(w.XNC, 3 * D, L.w_q_split, 3 * D, L.b_qkv, w.QC, D, BT, D, 3 * D, GAVA_EPI_H16, pr, stream, nullptr, 0, D, 0.125f));
-      } else if (fold1) {
-        TRY(ln(w.X, fs, nullptr, L.ln1_g, L.ln1_b, w.XNC, D, nullptr, 0, BT, D, pr, stream));     // the B*T CLS rows only
-        TRY(gemm_x(wl, w.XNC, D, L.w_qkv, D, L.b_qkv, w.QC, D, BT, D, D, GAVA_EPI_H16, pr, stream, nullptr, 0, D, 0.125f));
       } else {
-        TRY(gemm_x(wl, w.Xn, fs, L.w_qkv, D, L.b_qkv, w.QC, D, BT, D, D, GAVA_EPI_H16, pr, stream, nullptr, 0, D, 0.125f));
+        TRY(cls_queries(v, L, wl, fold1, w.X, w, w.QC, stream));
       }
-      if (two && hipStreamWaitEvent(s, g_side.join[i], 0) != hipSuccess) return GAVA_ELAUNCH;
-      {
-        gava_attention_args a{};
-        const unsigned short* q = (const unsigned short*)w.QKV;
-        a.q = w.QC; a.ld_q = D; a.q_batch_rows = 1;
-        a.k = q + D; a.v = q + 2 * D; a.ld_qkv = 3 * D;
-        a.side_k = sk; a.side_v = sk + D; a.ld_side = 2 * D;
-        a.out = w.MIXC; a.ld_out = S * D; a.split_out = sp;
-        a.batch = BT; a.heads = m->H; a.n_q = 1; a.n_kmain = n + 1;
-        a.n_g = G; a.T = Tm; a.has_summary = 1; a.prec = pr;
-        TRY(gava_attention(&a, stream));
-      }
+      TRY(side.join(i));
+      TRY(frame_attention(v, (const unsigned short*)w.QKV, w.QC, w.SIDEKV, w.MIXC, S * D, sp, stream));
       TRY(gemm_x(sp ? 0 : wl, w.MIXC, S * D, sp ? L.w_out_split : L.w_out, S * D, L.b_out, w.X, fs, BT, D, S * D, GAVA_EPI_F32, pr, stream, w.X, fs));
       TRY(ln(w.X, fs, nullptr, L.ln2_g, L.ln2_b, w.XNC, S * D, nullptr, 0, BT, D, pr, stream, sp));
       TRY(gemm_x(sp ? 0 : wl, w.XNC, S * D, sp ? L.w_fc1_split : L.w_fc1, S * D, L.b_fc1, w.HIDC, S * F, BT, F, S * D, GAVA_EPI_H16_QGELU, pr, stream, nullptr, 0, 0, 1.f, sp));
       TRY(gemm_x(sp ? 0 : wl, w.HIDC, S * F, sp ? L.w_fc2_split : L.w_fc2, S * F, L.b_fc2, w.X, fs, BT, D, S * F, GAVA_EPI_F32, pr, stream, w.X, fs));
     }
     if (debug_cls) {
-      if (pair && not_last_blk(i)) TRY(gava::join_rows(w.Xn, w.Xlo, fs, debug_cls + (long)i * BT * D, D, BT, D, pr, s));
+      if (pair && not_last) TRY(gava::join_rows(w.Xn, w.Xlo, fs, debug_cls + (long)i * BT * D, D, BT, D, pr, s));
       else TRY(gava::copy_rows(w.X, fs, debug_cls + (long)i * BT * D, BT, D, s));
     }
   }
 
   TRY(keep(1 + m->layers));
-  // ---- head (VitaCLIP_vision_encoder.py:126-130)
-  // split precision (3 MFMA passes): M = BT rows only, and its rounding lands directly on the output
-  TRY(ln(w.X, fs, nullptr, m->lnpost_g, m->lnpost_b, w.CLSPOST, 3 * D, nullptr, 0, BT, D, pr, stream, 1));
-  TRY(gemm(w.CLSPOST, 3 * D, m->w_proj, 3 * D, nullptr, w.PROJ, E, BT, E, 3 * D, GAVA_EPI_F32, pr, stream));
-  TRY(gava::mean_rows(w.PROJ, cls_x, m->B, m->T_in, E, s));
-  TRY(gava::mean_rows(w.SUMM, summary, BT / Tm, Tm, D, s));
-  return GAVA_OK;
+  return head(m, v, w.X, w, cls_x, summary, stream);
 }
 
 // Training forward that KEEPS the activations the backward needs instead of leaving them to be recomputed
@@ -568,136 +611,69 @@ extern "C" int gava_vision_forward_train(const gava_vision_model* m, const float
 extern "C" int gava_vision_forward_keep(const gava_vision_model* m, const float* x, float* cls_x, float* summary,
                                         const gava_vision_saved* sv, void* workspace, size_t workspace_bytes,
                                         gava_stream_t stream) {
-  TRY(check_vision(m));
-  if (m->w_lo) return GAVA_EINVAL;     // the weight-lo pass is an inference mode (gava_hip.h)
-  if ((!x && !m->clips) || !cls_x || !summary || !workspace || !sv || !sv->e0 || !sv->x || !sv->x1 || !sv->qkv || !sv->pre || !sv->sidekv)
-    return GAVA_EINVAL;
-  const VisionWs w = carve_vision(m, workspace, workspace_bytes);
-  if (w.total > workspace_bytes) return GAVA_EWORKSPACE;
-  hipStream_t s = (hipStream_t)stream;
+  // (the weight-lo pass is an inference mode: gava_hip.h)
+  if (!m || m->w_lo || !sv || !sv->e0 || !sv->x || !sv->x1 || !sv->qkv || !sv->pre || !sv->sidekv) return GAVA_EINVAL;
+  VisionWs w;
+  TRY(open_vision(m, x, cls_x, summary, workspace, workspace_bytes, &w));
   DeviceCtx& dc = device_ctx();
   std::lock_guard<std::mutex> lock(dc.mu);
-  SideStream& g_side = dc.side;
-  const int g = m->size / m->P, n = g * g, BT = m->B * m->T_in, R = BT * (n + 1);
-  const int D = m->D, F = m->F, E = m->E, G = m->G, Tm = m->T_model, pr = m->prec;
-  const int Kp = patch_k(m), SR = G + 2 * BT;
-  const long fs = (long)(n + 1) * D;
+  const VisionShape v(m);
+  const int BT = v.BT, R = v.R, D = v.D, F = v.F, pr = v.pr, SR = v.SR;
+  const long fs = v.fs;
   const size_t RD = (size_t)R * D;
-  {
-    gava_gemm_args a{};
-    TRY(patch_operand(m, x, w.HID, Kp, pr, stream, &a));
-    a.W = m->w_patch; a.ldw = Kp; a.bias = m->b_patch;
-    a.out = sv->e0; a.ldo = D; a.M = BT * n; a.N = D; a.K = Kp; a.epilogue = GAVA_EPI_F32_PATCH; a.prec = pr;
-    a.pos = m->pos_embed; a.time = m->time_embed; a.n_patches = n; a.T = m->T_in;
-    TRY(gava_gemm(&a, stream));
-  }
-  TRY(gava::cls_embed(sv->e0, m->cls_token, m->pos_embed, m->time_embed, BT, m->T_in, D, fs, s));
+  TRY(embed(m, v, x, 0, sv->e0, w.HID, stream));
   // LayerNorm folding as in the inference driver (norm1 / norm2 of the vision blocks are frozen, VitaCLIP_model.py:230-239, so
   // the folded weight copies stay valid while training; the backward recomputes the statistics from the kept fp32 stream and
-  // never needs the normalised activations).  GAVA_TRAIN_FOLD=0: separate LayerNorm launches (A/B).
-  static const bool fold_env = !(getenv("GAVA_TRAIN_FOLD") && getenv("GAVA_TRAIN_FOLD")[0] == '0');
-  static const bool fused_env = !(getenv("GAVA_FUSED_STATS") && getenv("GAVA_FUSED_STATS")[0] == '0');
-  const bool can_fold = fold_env && D % 64 == 0 && m->layers >= 1 && m->layer[0].w_fc1_fold && m->layer[0].w_qkv_fold;
-  const bool fused = fused_env && R >= 8192 && D % 256 == 0 && D <= 1024 && D >= 256;
-  Fold produce; produce.x16 = w.Xn; produce.ld_x16 = D; produce.rowsum = w.RSUM; produce.reduced = fused ? 1 : 0;
-  auto consume = [&](const float* s_, const float* t_) {
-    Fold c; c.s = s_; c.t = t_;
-    if (fused) c.partials = w.RSUM; else c.stats = w.STATS;
-    return c;
-  };
+  // never needs the normalised activations).
+  const bool can_fold = D % 64 == 0 && m->layer[0].w_fc1_fold && m->layer[0].w_qkv_fold;
+  const FoldPlan fp(w, R, D);
+  const Fold produce = fp.produce();
   // ln_pre, and with folding norm1 of block 0 in the same row pass
   if (can_fold) TRY(ln(sv->e0, D, nullptr, m->lnpre_g, m->lnpre_b, w.Xn, D, sv->x, D, R, D, pr, stream, 0, m->layer[0].ln1_g, m->layer[0].ln1_b));
   else TRY(ln(sv->e0, D, nullptr, m->lnpre_g, m->lnpre_b, nullptr, 0, sv->x, D, R, D, pr, stream));
   bool folded_in = false;   // Xn / RSUM already hold this block's un-normalised input and its row-sum partials
+  const Side side(dc.side, (hipStream_t)stream, m->layers);
   for (int i = 0; i < m->layers; ++i) {
     const gava_vision_layer& L = m->layer[i];
-    const unsigned short* wqkv = (const unsigned short*)L.w_qkv;
     float* Xin = sv->x + (size_t)i * RD;
     float* X1 = sv->x1 + (size_t)i * RD;
     float* Xout = sv->x + (size_t)(i + 1) * RD;
     unsigned short* QKV = (unsigned short*)sv->qkv + (size_t)i * R * 3 * D;
     unsigned short* PRE = (unsigned short*)sv->pre + (size_t)i * R * F;
     unsigned short* SKV = (unsigned short*)sv->sidekv + (size_t)i * SR * 2 * D;
-    const bool two = g_side.get() && m->layers <= 64;
-    gava_stream_t ss = two ? (gava_stream_t)g_side.s : stream;
-    if (two) {
-      if (hipEventRecord(g_side.fork[i], s) != hipSuccess || hipStreamWaitEvent(g_side.s, g_side.fork[i], 0) != hipSuccess)
-        return GAVA_ELAUNCH;
-    }
-    TRY(ln(Xin, fs, nullptr, nullptr, nullptr, w.CLS16, D, nullptr, 0, BT, D, pr, ss));
-    TRY(gemm(w.CLS16, D, L.w_cls, D, L.b_cls, w.CP, D, BT, D, D, GAVA_EPI_F32, pr, ss));
-    TRY(ln(w.CP, D, nullptr, L.sln_g, L.sln_b, w.CPn, D, nullptr, 0, BT, D, pr, ss));
-    TRY(gemm(w.CPn, D, L.w_sqkv, D, L.b_sqkv, w.SQKV, 3 * D, BT, 3 * D, D, GAVA_EPI_H16, pr, ss, nullptr, 0, D, 0.125f));
-    {
-      gava_attention_args a{};
-      const unsigned short* q = (const unsigned short*)w.SQKV;
-      a.q = q; a.k = q + D; a.v = q + 2 * D; a.ld_qkv = 3 * D; a.out = w.SMIX; a.ld_out = D;
-      a.batch = BT / Tm; a.heads = m->H; a.n_q = Tm; a.n_kmain = Tm; a.prec = pr;
-      TRY(gava_attention(&a, ss));
-    }
-    TRY(gemm(w.SMIX, D, L.w_sout, D, L.b_sout, w.SUMM, D, BT, D, D, GAVA_EPI_F32, pr, ss, w.CP, D));
-    TRY(gava::side_ln(L.global_prompts, L.local_prompts, w.CP, w.SUMM, L.ln1_g, L.ln1_b, w.SIDEn, G, Tm, BT, D, pr, (hipStream_t)ss));
-    TRY(gemm(w.SIDEn, D, wqkv + (long)D * D, D, L.b_qkv + D, SKV, 2 * D, SR, 2 * D, D, GAVA_EPI_H16, pr, ss));
-    if (two && hipEventRecord(g_side.join[i], g_side.s) != hipSuccess) return GAVA_ELAUNCH;
+    TRY(side.fork(i));
+    TRY(prompt_path(v, L, 0, w, Xin, nullptr, SKV, side.stream()));
+    TRY(side.done(i));
     const bool last_cls = i + 1 == m->layers && sv->last_q && sv->last_x1 && sv->last_pre;
     const bool fold1 = folded_in;                                               // set by the previous block's fc2
     const bool fold2 = can_fold && !last_cls && L.w_fc1_fold;                   // out_proj produces, fc1 consumes
     const bool fold1_next = can_fold && i + 1 < m->layers && m->layer[i + 1].w_qkv_fold;   // fc2 produces for the next qkv / K,V GEMM
-    const int resv = two ? side_cus(fold1) : 0;
+    const int resv = side.cus(fold1);
     if (!fold1 && !(i == 0 && can_fold)) TRY(ln(Xin, D, nullptr, L.ln1_g, L.ln1_b, w.Xn, D, nullptr, 0, R, D, pr, stream));
+    const float* qkv_s = fold1 ? L.qkv_fold_s : nullptr;
     if (last_cls) {
       // Last block, as in the inference driver: keys/values for every row, queries / out_proj / MLP for the B*T CLS
       // rows only (VitaCLIP_vision_encoder.py:126 reads x[:,0]).  Kept: K/V in the QKV slot, the CLS queries, the CLS
       // rows of the stream after attention, the CLS pre-activations.
       unsigned short* QC = (unsigned short*)sv->last_q;
       unsigned short* PREC = (unsigned short*)sv->last_pre;
-      if (fold1) {   // norm1 folded into the K/V GEMM; the B*T CLS queries get a LayerNorm of their own
-        Fold c = consume(L.qkv_fold_s + D, L.qkv_fold_t + D);
-        TRY(gemm(w.Xn, D, (const unsigned short*)L.w_qkv_fold + (long)D * D, D, nullptr, QKV + D, 3 * D, R, 2 * D, D, GAVA_EPI_H16, pr, stream,
-                 nullptr, 0, 0, 1.f, 0, nullptr, &c, resv));
-        TRY(ln(Xin, fs, nullptr, L.ln1_g, L.ln1_b, w.XNC, D, nullptr, 0, BT, D, pr, stream));
-        TRY(gemm(w.XNC, D, L.w_qkv, D, L.b_qkv, QC, D, BT, D, D, GAVA_EPI_H16, pr, stream, nullptr, 0, D, 0.125f));
-      } else {
-        TRY(gemm(w.Xn, D, wqkv + (long)D * D, D, L.b_qkv + D, QKV + D, 3 * D, R, 2 * D, D, GAVA_EPI_H16, pr, stream, nullptr, 0, 0, 1.f, 0, nullptr, nullptr, resv));
-        TRY(gemm(w.Xn, fs, L.w_qkv, D, L.b_qkv, QC, D, BT, D, D, GAVA_EPI_H16, pr, stream, nullptr, 0, D, 0.125f));
-      }
-      if (two && hipStreamWaitEvent(s, g_side.join[i], 0) != hipSuccess) return GAVA_ELAUNCH;
-      {
-        gava_attention_args a{};
-        a.q = QC; a.ld_q = D; a.q_batch_rows = 1;
-        a.k = QKV + D; a.v = QKV + 2 * D; a.ld_qkv = 3 * D;
-        a.side_k = SKV; a.side_v = SKV + D; a.ld_side = 2 * D;
-        a.out = w.MIXC; a.ld_out = D;
-        a.batch = BT; a.heads = m->H; a.n_q = 1; a.n_kmain = n + 1;
-        a.n_g = G; a.T = Tm; a.has_summary = 1; a.prec = pr;
-        TRY(gava_attention(&a, stream));
-      }
+      TRY(qkv_gemm(v, L, 0, true, fp, qkv_s, nullptr, QKV, resv, stream));
+      TRY(cls_queries(v, L, 0, fold1, Xin, w, QC, stream));
+      TRY(side.join(i));
+      TRY(frame_attention(v, QKV, QC, SKV, w.MIXC, D, 0, stream));
       TRY(gemm(w.MIXC, D, L.w_out, D, L.b_out, sv->last_x1, D, BT, D, D, GAVA_EPI_F32, pr, stream, Xin, fs));
       TRY(ln(sv->last_x1, D, nullptr, L.ln2_g, L.ln2_b, w.XNC, D, nullptr, 0, BT, D, pr, stream));
       TRY(gemm(w.XNC, D, L.w_fc1, D, L.b_fc1, w.HIDC, F, BT, F, D, GAVA_EPI_H16_QGELU, pr, stream, nullptr, 0, 0, 1.f, 0, PREC));
       TRY(gemm(w.HIDC, F, L.w_fc2, F, L.b_fc2, Xout, fs, BT, D, F, GAVA_EPI_F32, pr, stream, sv->last_x1, D));
       continue;
     }
-    if (fold1) {
-      Fold c = consume(L.qkv_fold_s, L.qkv_fold_t);
-      TRY(gemm(w.Xn, D, L.w_qkv_fold, D, nullptr, QKV, 3 * D, R, 3 * D, D, GAVA_EPI_H16, pr, stream, nullptr, 0, D, 0.125f, 0, nullptr, &c, resv));
-    } else {
-      TRY(gemm(w.Xn, D, L.w_qkv, D, L.b_qkv, QKV, 3 * D, R, 3 * D, D, GAVA_EPI_H16, pr, stream, nullptr, 0, D, 0.125f, 0, nullptr, nullptr, resv));
-    }
-    if (two && hipStreamWaitEvent(s, g_side.join[i], 0) != hipSuccess) return GAVA_ELAUNCH;
-    {
-      gava_attention_args a{};
-      a.q = QKV; a.k = QKV + D; a.v = QKV + 2 * D; a.ld_qkv = 3 * D;
-      a.side_k = SKV; a.side_v = SKV + D; a.ld_side = 2 * D;
-      a.out = w.MIX; a.ld_out = D;
-      a.batch = BT; a.heads = m->H; a.n_q = n + 1; a.n_kmain = n + 1;
-      a.n_g = G; a.T = Tm; a.has_summary = 1; a.prec = pr;
-      TRY(gava_attention(&a, stream));
-    }
+    TRY(qkv_gemm(v, L, 0, false, fp, qkv_s, nullptr, QKV, resv, stream));
+    TRY(side.join(i));
+    TRY(frame_attention(v, QKV, nullptr, SKV, w.MIX, D, 0, stream));
     if (fold2) {
       TRY(gemm(w.MIX, D, L.w_out, D, L.b_out, X1, D, R, D, D, GAVA_EPI_F32, pr, stream, Xin, D, 0, 1.f, 0, nullptr, &produce));
-      if (!fused) TRY(gava_row_stats(w.RSUM, D / 64, D, R, w.STATS, stream));
-      Fold c = consume(L.fc1_fold_s, L.fc1_fold_t);
+      TRY(fp.stats(stream));
+      Fold c = fp.consume(L.fc1_fold_s, L.fc1_fold_t);
       TRY(gemm(w.Xn, D, L.w_fc1_fold, D, nullptr, w.HID, F, R, F, D, GAVA_EPI_H16_QGELU, pr, stream, nullptr, 0, 0, 1.f, 0, PRE, &c));
     } else {
       TRY(gemm(w.MIX, D, L.w_out, D, L.b_out, X1, D, R, D, D, GAVA_EPI_F32, pr, stream, Xin, D));
@@ -706,18 +682,13 @@ extern "C" int gava_vision_forward_keep(const gava_vision_model* m, const float*
     }
     if (fold1_next) {
       TRY(gemm(w.HID, F, L.w_fc2, F, L.b_fc2, Xout, D, R, D, F, GAVA_EPI_F32, pr, stream, X1, D, 0, 1.f, 0, nullptr, &produce));
-      if (!fused) TRY(gava_row_stats(w.RSUM, D / 64, D, R, w.STATS, stream));
+      TRY(fp.stats(stream));
     } else {
       TRY(gemm(w.HID, F, L.w_fc2, F, L.b_fc2, Xout, D, R, D, F, GAVA_EPI_F32, pr, stream, X1, D));
     }
     folded_in = fold1_next;
   }
-  const float* Xf = sv->x + (size_t)m->layers * RD;
-  TRY(ln(Xf, fs, nullptr, m->lnpost_g, m->lnpost_b, w.CLSPOST, 3 * D, nullptr, 0, BT, D, pr, stream, 1));
-  TRY(gemm(w.CLSPOST, 3 * D, m->w_proj, 3 * D, nullptr, w.PROJ, E, BT, E, 3 * D, GAVA_EPI_F32, pr, stream));
-  TRY(gava::mean_rows(w.PROJ, cls_x, m->B, m->T_in, E, s));
-  TRY(gava::mean_rows(w.SUMM, summary, BT / Tm, Tm, D, s));
-  return GAVA_OK;
+  return head(m, v, sv->x + (size_t)m->layers * RD, w, cls_x, summary, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -2008,16 +2008,23 @@ int launch_prec(const GemmParams& gp, int epi, hipStream_t s) {
   const long tiles256 = (long)((gp.M + 255) / 256) * (gp.N / 256);
   // ... and, since the fp32-output kernels use the natural column order (64 contiguous bytes per row and instruction in
   // the residual loads and the stores), also for the shallow fp32 GEMM: out 0.251 vs 0.268 ms on the 128^2 kernel
-  if (gp.N % 256 == 0 && fits32 &&
-      (gp.N >= 1536 || (gp.K >= 2048 && tiles256 >= 512) || (epi == GAVA_EPI_F32 && tiles256 >= 512) || variant == 3 ||
-       (epi == GAVA_EPI_F32_PATCH && tiles256 >= 512 && patch_on_256())))
-    return launch_256<P, 3>(gp, epi, s);
+  const bool on_256 = epi == GAVA_EPI_F32_PATCH
+                          ? gava::gemm_patch_on_persistent(gp.M, gp.N, gp.lda, gp.ldw)
+                          : gp.N >= 1536 || (gp.K >= 2048 && tiles256 >= 512) || (epi == GAVA_EPI_F32 && tiles256 >= 512);
+  if (gp.N % 256 == 0 && fits32 && (on_256 || variant == 3)) return launch_256<P, 3>(gp, epi, s);
   return launch_tile<P, 128, 128, 2>(gp, epi, s);
 }
 
 }  // namespace
 
 namespace gava {
+// launch_prec's route for the two-pass patch embedding's GEMM (EPI_F32_PATCH on the 16-bit patch matrix): the persistent 256^2
+// kernel when the batch gives it enough tiles; forward.hip's patch_operand builds the patch matrix for it in just these cases
+bool gemm_patch_on_persistent(int M, int N, long lda, long ldw) {
+  const bool fits = (unsigned long long)(M + 256) * lda < (1ull << 31) && (unsigned long long)N * ldw < (1ull << 31);
+  return N % 256 == 0 && fits && (long)((M + 255) / 256) * (N / 256) >= 512 && patch_on_256();
+}
+
 // the conditions of launch_prec / launch_256 for the HL instantiations; GAVA_PAIR_STREAM=0: never (A/B against the fp32 stream)
 bool gemm_takes_pair(int M, int N, int K, long lda, long ldw) {
   const char* e = getenv("GAVA_PAIR_STREAM");      // read per call: the tests switch it inside one process

@@ -2,7 +2,7 @@
 """Same-box A/B of whole-forward settings that are chosen by environment variables (one fresh process per setting and
 round, alternating, so that box-to-box and thermal drift cancel):
 
-    python tools/ab_env.py "base:" "noprefuse:GAVA_NO_PREFUSE=1" "lib2:GAVA_HIP_LIB=gava_clip_amd/libgava_hip_x.so" [--rounds 3] [--config c2]
+    python tools/ab_env.py "base:" "fp32stream:GAVA_PAIR_STREAM=0" "lib2:GAVA_HIP_LIB=gava_clip_amd/libgava_hip_x.so" [--rounds 3] [--config c2]
 
 Each child runs the bench's forward loop (tools/ab_env.py --child) and prints ms/forward."""
 import os, subprocess, sys, statistics
