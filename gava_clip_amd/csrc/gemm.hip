@@ -186,17 +186,15 @@ void gemm_kernel(const GemmParams p) {
       if (EPI == GAVA_EPI_F32_PATCH && p.clips) {
         // uint8 source: every element is one pixel of the (virtual) preprocessed clip - temporal crop, normalisation,
         // bilinear resize and centre crop evaluated here (clip_pixel.h), nothing but the decoded frames is read from HBM
-        const gava_clip_desc& cd = p.clips[b];
-        int f = cd.t_st + t * cd.rate;
-        f = f < cd.n_frames ? f : cd.n_frames - 1;
+        const ClipGeom cd = clip_geom(p.clips[b]);
+        const int f = clip_frame(cd, t), form = clip_form(cd, t);
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
           const int kq = k + q;
           float v = 0.f;
           if (kq < Kreal) {
             const int c = kq / P2, rem = kq - c * P2, ky = rem / p.patch, kx = rem - ky * p.patch;
-            v = clip_pixel1(cd.frames, cd.height, cd.width, cd.h_st, cd.w_st, cd.scale_h, cd.scale_w, p.clut, 0.f, 1.f, f, c,
-                            py * p.patch + ky, px * p.patch + kx);
+            v = clip_pixel1(cd, p.clut, 0.f, 1.f, f, form, c, py * p.patch + ky, px * p.patch + kx);
           }
           pe[ti][q] = v;
         }

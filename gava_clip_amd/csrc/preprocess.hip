@@ -1,5 +1,6 @@
-// Clip preprocessing on the GPU: the evaluation data path of the reference
-// (video_dataset/dataset.py:117-139) from decoded uint8 RGB frames to the fp32 model input.
+// Clip preprocessing on the GPU: the data path of the reference from decoded uint8 RGB frames to the fp32
+// model input - the evaluation branch (video_dataset/dataset.py:117-139, which its train loader uses too) and the
+// random-sample branch (:93-114, auto_augment=None), told apart by the descriptor alone (gava_clip_desc).
 // One thread per output pixel and frame, all three channels: the 4 bilinear taps are 4 x 3 adjacent bytes, the
 // three stores are coalesced planes.  HBM-bound: 3 B in (at most 12 touched) and 12 B out per pixel.
 #include "common.h"
@@ -20,12 +21,31 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const PrepParams p) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x;
   const int y = blockIdx.y, t = blockIdx.z;
   if (x >= p.size) return;
-  int f = p.g.t_st + t * p.g.rate;
-  f = f < p.g.n_frames ? f : p.g.n_frames - 1;
+  const int f = clip_frame(p.g, t), form = clip_form(p.g, t);
 #pragma unroll
   for (int c = 0; c < 3; ++c)
-    p.out[c * p.out_stride_c + t * p.out_stride_t + (long)y * p.size + x] =
-        clip_pixel1(p.g.frames, p.g.height, p.g.width, p.g.h_st, p.g.w_st, p.g.scale_h, p.g.scale_w, p.lut, p.mean[c], p.std[c], f, c, y, x);
+    p.out[c * p.out_stride_c + t * p.out_stride_t + (long)y * p.size + x] = clip_pixel1(p.g, p.lut, p.mean[c], p.std[c], f, form, c, y, x);
+}
+
+// The whole batch in one launch: workgroup = 64 pixels x 4 rows of one frame of one clip (grid: row chunks, row groups,
+// clips x frames), the clip's descriptor read through the scalar cache.  A wave stores 256 contiguous bytes per channel plane;
+// its byte loads walk two source rows.  Videos of different sizes in one batch only change what each workgroup reads.
+struct PrepBatchParams {
+  const gava_clip_desc* clips; const float* lut;
+  float* out;
+  long out_stride_b, out_stride_c, out_stride_t;
+  int T, size;
+};
+
+__global__ __launch_bounds__(256) void preprocess_clips_kernel(const PrepBatchParams p) {
+  const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
+  const int b = blockIdx.z / p.T, t = blockIdx.z - b * p.T;
+  if (x >= p.size || y >= p.size) return;
+  const ClipGeom g = clip_geom(p.clips[b]);
+  const int f = clip_frame(g, t), form = clip_form(g, t);
+  float* o = p.out + b * p.out_stride_b + t * p.out_stride_t + (long)y * p.size + x;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) o[c * p.out_stride_c] = clip_pixel1(g, p.lut, 0.f, 1.f, f, form, c, y, x);
 }
 
 // Patch matrix (see gava_patchify_args): one workgroup per (patch row gy, channel c, frame f): P image rows of `size`
@@ -44,13 +64,12 @@ __global__ __launch_bounds__(256) void patchify_kernel(const PatchifyParams p) {
   const int n_vec = p.P * p.size / VEC, PP = p.P * p.P;
   const float* plane = nullptr;
   ClipGeom cg{};
-  int fsrc = 0;
+  int fsrc = 0, form = 0;
   if (p.x) plane = p.x + (((long)b * 3 + c) * p.T + t) * p.size * p.size + (long)gy * p.P * p.size;
   else {
-    const gava_clip_desc d = p.clips[b];
-    cg = ClipGeom{d.frames, d.n_frames, d.height, d.width, d.t_st, d.rate, d.h_st, d.w_st, d.scale_h, d.scale_w};
-    fsrc = d.t_st + t * d.rate;
-    fsrc = fsrc < d.n_frames ? fsrc : d.n_frames - 1;
+    cg = clip_geom(p.clips[b]);
+    fsrc = clip_frame(cg, t);
+    form = clip_form(cg, t);
   }
   unsigned short* orow0 = p.out + ((long)f * p.g * p.g + (long)gy * p.g) * p.ldo + c * PP;
   for (int i = threadIdx.x; i < n_vec; i += 256) {
@@ -69,8 +88,7 @@ __global__ __launch_bounds__(256) void patchify_kernel(const PatchifyParams p) {
     } else {
 #pragma unroll
       for (int e = 0; e < VEC; ++e)
-        v[e] = clip_pixel1(cg.frames, cg.height, cg.width, cg.h_st, cg.w_st, cg.scale_h, cg.scale_w, p.lut, 0.f, 1.f, fsrc, c,
-                           gy * p.P + iy, x0 + e);
+        v[e] = clip_pixel1(cg, p.lut, 0.f, 1.f, fsrc, form, c, gy * p.P + iy, x0 + e);
     }
     const int px = x0 / p.P, ix = x0 - px * p.P;
     unsigned short* o = orow0 + (long)px * p.ldo + iy * p.P + ix;
@@ -136,6 +154,25 @@ extern "C" int gava_clip_geometry(gava_clip_desc* d, int T, int rate, int size, 
   d->rate = rate;
   d->scale_h = (float)d->height / (float)new_h;
   d->scale_w = (float)d->width / (float)new_w;
+  d->box_y = 0; d->box_x = 0; d->box_h = d->height; d->box_w = d->width;   // the evaluation branch resizes the whole frame
+  d->lerp4_frames = 0;   // (torch switches kernels at resized height + width <= 128; this branch keeps the separable form it always had)
+  d->frame_idx = nullptr;
+  return GAVA_OK;
+}
+
+extern "C" int gava_clip_geometry_box(gava_clip_desc* d, int size, int T, const int* idx_host, const int* idx_dev, int i, int j,
+                                      int h, int w) {
+  if (!d || d->n_frames <= 0 || d->height <= 0 || d->width <= 0 || size <= 0 || T <= 0 || !idx_host || !idx_dev) return GAVA_EINVAL;
+  if (h <= 0 || w <= 0 || i < 0 || j < 0 || i > d->height - h || j > d->width - w) return GAVA_EINVAL;   // empty / leaves the frame
+  for (int t = 0; t < T; ++t)
+    if (idx_host[t] < 0 || idx_host[t] >= d->n_frames) return GAVA_EINVAL;
+  d->t_st = 0; d->rate = 1; d->h_st = 0; d->w_st = 0;
+  // transform.py:570-577 interpolates the cropped h x w tensor to size x size: torch's scale is (float)in / out
+  d->scale_h = (float)h / (float)size;
+  d->scale_w = (float)w / (float)size;
+  d->box_y = i; d->box_x = j; d->box_h = h; d->box_w = w;
+  d->lerp4_frames = 2 * size <= 128 ? T : 0;   // which CPU kernel F.interpolate picks for a size x size output
+  d->frame_idx = idx_dev;
   return GAVA_OK;
 }
 
@@ -149,13 +186,27 @@ extern "C" int gava_preprocess_clip(const gava_preprocess_args* a, gava_stream_t
   const int e = gava_clip_geometry(&d, a->T, a->rate, a->size, a->first_temporal_view, a->first_spatial_view);
   if (e != GAVA_OK) return e;
   PrepParams p;
-  p.g = ClipGeom{d.frames, d.n_frames, d.height, d.width, d.t_st, d.rate, d.h_st, d.w_st, d.scale_h, d.scale_w};
+  p.g = ClipGeom{d.frames, d.n_frames, d.height, d.width, d.t_st, d.rate, d.h_st, d.w_st, d.scale_h, d.scale_w,
+                 d.box_y, d.box_x, d.box_h, d.box_w, d.lerp4_frames, d.frame_idx};
   p.out = a->out; p.out_stride_c = a->out_stride_c; p.out_stride_t = a->out_stride_t;
   p.T = a->T; p.size = a->size;
   for (int c = 0; c < 3; ++c) { p.mean[c] = a->mean[c]; p.std[c] = a->std[c]; }
   p.lut = a->lut;
   dim3 block(256), grid((a->size + 255) / 256, a->size, a->T);
   hipLaunchKernelGGL(preprocess_kernel, grid, block, 0, (hipStream_t)stream, p);
+  if (hipGetLastError() != hipSuccess) return GAVA_ELAUNCH;
+  return GAVA_OK;
+}
+
+extern "C" int gava_preprocess_clips(const gava_preprocess_clips_args* a, gava_stream_t stream) {
+  if (!a || !a->clips || !a->lut || !a->out) return GAVA_EINVAL;
+  if (a->B <= 0 || a->T <= 0 || a->size <= 0 || (long)a->B * a->T > 65535 || (a->size + 3) / 4 > 65535) return GAVA_EINVAL;
+  PrepBatchParams p;
+  p.clips = a->clips; p.lut = a->lut; p.out = a->out;
+  p.out_stride_b = a->out_stride_b; p.out_stride_c = a->out_stride_c; p.out_stride_t = a->out_stride_t;
+  p.T = a->T; p.size = a->size;
+  dim3 block(64, 4), grid((a->size + 63) / 64, (a->size + 3) / 4, a->B * a->T);
+  hipLaunchKernelGGL(preprocess_clips_kernel, grid, block, 0, (hipStream_t)stream, p);
   if (hipGetLastError() != hipSuccess) return GAVA_ELAUNCH;
   return GAVA_OK;
 }

@@ -23,7 +23,8 @@ EXPORTS = ["gava_abi_version", "gava_gemm", "gava_layernorm", "gava_attention",
            "gava_preprocess_clip", "gava_layernorm_backward", "gava_qgelu_backward", "gava_attention_backward",
            "gava_text_forward_train", "gava_vision_forward_train", "gava_attention_backward_workspace_bytes", "gava_vision_forward_keep", "gava_row_stats",
            "gava_probe_fc1_enable", "gava_probe_fc1_read", "gava_clip_geometry", "gava_patchify", "gava_attention_f32",
-           "gava_gemm_aligned_walk", "gava_vision_pair_stream", "gava_struct_sizes"]
+           "gava_gemm_aligned_walk", "gava_vision_pair_stream", "gava_struct_sizes", "gava_clip_geometry_box",
+           "gava_preprocess_clips"]
 
 _vp, _fp, _ip = C.c_void_p, C.c_void_p, C.c_void_p  # all device pointers travel as void*
 
@@ -66,7 +67,9 @@ class AttentionArgs(C.Structure):
 class ClipDesc(C.Structure):
     _fields_ = [("frames", _vp), ("n_frames", C.c_int), ("height", C.c_int), ("width", C.c_int),
                 ("t_st", C.c_int), ("rate", C.c_int), ("h_st", C.c_int), ("w_st", C.c_int),
-                ("scale_h", C.c_float), ("scale_w", C.c_float)]
+                ("scale_h", C.c_float), ("scale_w", C.c_float),
+                ("box_y", C.c_int), ("box_x", C.c_int), ("box_h", C.c_int), ("box_w", C.c_int), ("lerp4_frames", C.c_int),
+                ("frame_idx", _ip)]
 
 
 class VisionLayer(C.Structure):
@@ -118,6 +121,11 @@ class PreprocessArgs(C.Structure):
                 ("T", C.c_int), ("rate", C.c_int), ("size", C.c_int),
                 ("out", _fp), ("out_stride_c", C.c_int64), ("out_stride_t", C.c_int64),
                 ("first_temporal_view", C.c_int), ("first_spatial_view", C.c_int), ("lut", _fp)]
+
+
+class PreprocessClipsArgs(C.Structure):
+    _fields_ = [("clips", _vp), ("lut", _fp), ("B", C.c_int), ("T", C.c_int), ("size", C.c_int),
+                ("out", _fp), ("out_stride_b", C.c_int64), ("out_stride_c", C.c_int64), ("out_stride_t", C.c_int64)]
 
 
 class PatchifyArgs(C.Structure):
@@ -217,6 +225,9 @@ def load():
     lib.gava_attention_backward_workspace_bytes.restype = C.c_size_t
     lib.gava_clip_geometry.argtypes = [C.POINTER(ClipDesc), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     lib.gava_clip_geometry.restype = C.c_int
+    lib.gava_clip_geometry_box.argtypes = [C.POINTER(ClipDesc), C.c_int, C.c_int, C.POINTER(C.c_int), _ip] + [C.c_int] * 4
+    lib.gava_clip_geometry_box.restype = C.c_int
+    lib.gava_preprocess_clips.argtypes, lib.gava_preprocess_clips.restype = [C.POINTER(PreprocessClipsArgs), _vp], C.c_int
     lib.gava_gemm_aligned_walk.argtypes, lib.gava_gemm_aligned_walk.restype = [C.c_int, C.c_int, C.c_int], C.c_int
     lib.gava_probe_fc1_enable.argtypes = [C.c_int]
     lib.gava_probe_fc1_read.argtypes = [C.POINTER(C.c_float), C.c_int]
@@ -231,7 +242,7 @@ def load():
     lib.gava_vision_pair_stream.argtypes, lib.gava_vision_pair_stream.restype = [C.POINTER(VisionModel)], C.c_int
     # the header the library was compiled from against the mirrors above (gava_abi_version ties library and header)
     mirrors = [GemmArgs, LayerNormArgs, AttentionArgs, AttentionF32Args, ClipDesc, VisionLayer, VisionLayer8, VisionModel, TextLayer,
-               TextModel, LayerNormBwdArgs, AttentionBwdArgs, VisionSaved, PreprocessArgs, PatchifyArgs]
+               TextModel, LayerNormBwdArgs, AttentionBwdArgs, VisionSaved, PreprocessArgs, PatchifyArgs, PreprocessClipsArgs]
     sizes = (C.c_size_t * len(mirrors))()
     lib.gava_struct_sizes.argtypes, lib.gava_struct_sizes.restype = [C.POINTER(C.c_size_t), C.c_int], C.c_int
     if lib.gava_struct_sizes(sizes, len(mirrors)) != len(mirrors):
@@ -393,6 +404,19 @@ def preprocess_clip(frames_u8, out, *, T, rate, size, mean, std, first_temporal_
     check(load().gava_preprocess_clip(C.byref(a), stream_ptr()), "gava_preprocess_clip")
 
 
+def preprocess_clips(desc, out, *, T, size, lut):
+    """The whole batch in one launch: desc = device array of B gava_clip_desc (clip_descriptors / clip_descriptors_box),
+    out = fp32 [B][3][T][size][size] whose size x size planes are contiguous, lut = clip_lut(...)."""
+    B = out.shape[0]
+    assert out.dtype == torch.float32 and tuple(out.shape) == (B, 3, T, size, size)
+    assert out.stride(4) == 1 and out.stride(3) == size, "output planes must be contiguous"
+    assert desc.dtype == torch.uint8 and desc.numel() == B * C.sizeof(ClipDesc) and lut is not None
+    a = PreprocessClipsArgs()
+    a.clips, a.lut, a.B, a.T, a.size = ptr(desc), ptr(lut), B, T, size
+    a.out, a.out_stride_b, a.out_stride_c, a.out_stride_t = ptr(out), out.stride(0), out.stride(1), out.stride(2)
+    check(load().gava_preprocess_clips(C.byref(a), stream_ptr()), "gava_preprocess_clips")
+
+
 def patchify(out, *, B, T, size, patch, prec, x=None, clips=None, clip_lut=None):
     """16-bit patch matrix [B*T*(size/patch)^2, ldo] of the fp32 clips `x` (B,3,T,size,size) or of the uint8 videos behind
     `clips` (clip_descriptors): the A operand of the patch-embedding GEMM (gemm(A, ..., epilogue=EPI_F32_PATCH))."""
@@ -462,3 +486,23 @@ def clip_descriptors(videos, *, T, rate, size, first_temporal_view=False, first_
               "gava_clip_geometry")
     host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
     return host.to(videos[0].device), list(videos)
+
+
+def clip_descriptors_box(videos, draws, *, size):
+    """The random-sample branch (dataset.py:93-114, auto_augment=None): `draws` holds one (idx, i, j, h, w) per video -
+    source frame indices and the crop box of transform.py:503-542 - checked by the library (gava_clip_geometry_box).
+    -> (uint8 device tensor holding an array of gava_clip_desc, keep-alive list: the videos and the device frame tables)."""
+    lib = load()
+    arr = (ClipDesc * len(videos))()
+    T = len(draws[0][0])
+    assert all(len(d[0]) == T for d in draws) and len(draws) == len(videos)
+    dev = videos[0].device
+    tables = torch.tensor([list(d[0]) for d in draws], dtype=torch.int32).to(dev)       # one copy for the batch
+    for n, (v, (idx, i, j, h, w)) in enumerate(zip(videos, draws)):
+        assert v.is_cuda and v.dtype == torch.uint8 and v.dim() == 4 and v.shape[-1] == 3 and v.is_contiguous()
+        arr[n].frames, arr[n].n_frames, arr[n].height, arr[n].width = ptr(v), v.shape[0], v.shape[1], v.shape[2]
+        host = (C.c_int * T)(*[int(x) for x in idx])
+        check(lib.gava_clip_geometry_box(C.byref(arr[n]), size, T, host, ptr(tables[n]), int(i), int(j), int(h), int(w)),
+              "gava_clip_geometry_box")
+    host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
+    return host.to(dev), list(videos) + [tables]

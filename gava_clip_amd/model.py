@@ -1030,21 +1030,31 @@ class VitaCLIP(nn.Module, _HipHost):
     def forward_frames(self, videos, preprocessor, memory=None, video_nte=None, desc_wise=False):
         """forward() on DECODED videos instead of a preprocessed batch: `videos` is a list of uint8 device tensors
         [n_i, H_i, W_i, 3] (PyAV's to_rgb().to_ndarray() order), `preprocessor` a gava_clip_amd.preprocess.ClipPreprocessor
-        (the evaluation branch of video_dataset/dataset.py:117-139).  The patch-embedding GEMM reads the frames themselves
-        (temporal crop, normalisation, bilinear resize and centre crop per loaded pixel): same logits, bit for bit, as
-        forward(preprocessor.batch(videos)), without the fp32 clip ever being written to HBM - 4x fewer input bytes.
-        Inference only (the training branch of the reference's data path augments on the host)."""
-        if torch.is_grad_enabled():
-            raise hip.GavaError("forward_frames is the evaluation data path: call it under torch.no_grad()")
+        (video_dataset/dataset.py:117-139, the branch the reference evaluates AND trains with: its train loader sets
+        random_sample=False, dataloader.py:89-102) or a TrainClipPreprocessor (the random-sample branch, :93-114, which
+        draws its frames and crop box here, one sample() per video in batch order).  The patch embedding reads the frames
+        themselves (frame selection, normalisation, bilinear resize and crop per loaded pixel): same logits, bit for bit,
+        as forward(preprocessor.batch(videos)) wherever forward() takes the two-pass patch embedding too (big batches;
+        small fp32 batches take the im2col-free GEMM, equal to the rounding of its 16-bit operands), without the fp32 clip
+        ever being written to HBM - 4x fewer input bytes.
+
+        Training: on a model in train() mode this runs under autograd like forward() - loss.backward() reaches every
+        trainable parameter; the videos themselves get no gradient.  The backward never re-reads the input, in either
+        activation mode (kept activations, or GAVA_KEEP_ACT_GB=0: recomputation from the saved fp32 input of every
+        block, the first of which is the embedding's output): `videos` may be released as soon as this call returns.
+        A model in eval() mode with grad enabled is refused: that is the evaluation path with a forgotten
+        torch.no_grad(), which would keep every block's activations alive."""
+        if torch.is_grad_enabled() and not self.training:
+            raise hip.GavaError("forward_frames on a model in eval() mode is the evaluation data path: call it under "
+                                "torch.no_grad(), or put the model in train() mode to train through it")
         pre = preprocessor
         assert pre.spatial_size == self._shape["size"], "the preprocessor's crop size must be the model's input size"
         dev = videos[0].device
         with torch.cuda.device(dev):
             pre.check(videos)
-            desc, keep = hip.clip_descriptors(videos, T=pre.num_frames, rate=pre.sampling_rate, size=pre.spatial_size,
-                                              first_temporal_view=pre.num_temporal_views > 1,
-                                              first_spatial_view=pre.num_spatial_views == 3)
+            desc, keep = pre.descriptors([v.contiguous() for v in videos])
             clips = (desc, len(videos), pre.num_frames, pre.lut(dev), dev)
+            # (`keep` - the contiguous videos and the frame tables - lives until the patch embedding is enqueued, no longer)
             return self._forward_impl(desc, memory, video_nte, desc_wise, clips=clips)
 
     def _forward_impl(self, x, memory, video_nte, desc_wise, clips=None):
@@ -1108,7 +1118,7 @@ class VitaCLIP(nn.Module, _HipHost):
         if train_vision:
             # differentiable vision tower (gava_clip_amd/training.py): gradients of the prompt parameters
             from .training import VisionTowerFn
-            cls_x, summary = VisionTowerFn.apply(self, x, *[p for _, p in self._vision_trainables()])
+            cls_x, summary = VisionTowerFn.apply(self, x, clips, *[p for _, p in self._vision_trainables()])
         else:
             cls_x, summary = self.encode_video(x, clips=clips)
         # The all-gather of the clip embeddings goes out on the main stream as soon as the vision tower is enqueued - BEFORE the

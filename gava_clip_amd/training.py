@@ -402,22 +402,26 @@ def vision_backward(model, saved, dcls_x, B, T, dsummary=None, kept=None):
 
 class VisionTowerFn(torch.autograd.Function):
     """cls_x = f(x; prompt parameters) with the HIP vision tower in both directions.  `params` are the trainable vision
-    parameters in `_vision_trainables` order (they enter only so that autograd routes their gradients)."""
+    parameters in `_vision_trainables` order (they enter only so that autograd routes their gradients).
+    clips: None, or the uint8 source of VitaCLIP.forward_frames (encode_video's `clips`; x is then the descriptor tensor).
+    Either way the backward starts from what the forward kept (the embedding output and the blocks' activations, or in
+    recompute mode the fp32 input of every block): the input is read by the forward's patch embedding only, so neither the
+    descriptors nor the decoded videos are held for the backward."""
 
     @staticmethod
-    def forward(fctx, model, x, *params):
+    def forward(fctx, model, x, clips, *params):
         sh = model._shape
-        B, _, T = x.shape[:3]
+        B, T = (clips[1], clips[2]) if clips is not None else (x.shape[0], x.shape[2])
         n1 = (sh["size"] // sh["P"]) ** 2 + 1
         fctx.model, fctx.BT = model, (B, T)
         if kept_bytes(model, B, T) <= model.keep_activation_bytes:
             fctx.kept = alloc_kept(model, B, T, x.device)
-            cls_x, summary = model.encode_video(x, kept=fctx.kept)
+            cls_x, summary = model.encode_video(x, kept=fctx.kept, clips=clips)
             fctx.save_for_backward()
         else:
             fctx.kept = None
             saved = torch.empty(sh["layers"] + 2, B * T * n1, sh["D"], dtype=torch.float32, device=x.device)
-            cls_x, summary = model.encode_video(x, saved=saved)
+            cls_x, summary = model.encode_video(x, saved=saved, clips=clips)
             fctx.save_for_backward(saved)
         return cls_x, summary
 
@@ -434,4 +438,4 @@ class VisionTowerFn(torch.autograd.Function):
         for name, p in _vision_trainables(model):
             gi = g.get(name)
             out.append(gi.reshape(p.shape).to(p.dtype) if (gi is not None and p.requires_grad) else None)
-        return (None, None, *out)
+        return (None, None, None, *out)

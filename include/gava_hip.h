@@ -74,9 +74,35 @@ typedef struct {
   int t_st, rate;                   /* frame(t) = min(t_st + t*rate, n_frames-1)                    */
   int h_st, w_st;                   /* crop offset inside the resized frame                          */
   float scale_h, scale_w;           /* source / resized extent (align_corners = False)               */
+  /* Source box inside the decoded frame: the bilinear taps read rows box_y + [0, box_h) and columns box_x + [0, box_w) only,
+   * and the neighbour of the box's last row / column is that row / column itself (the reference interpolates the cropped
+   * tensor, transform.py:570-577); the row pitch stays `width`.  Evaluation branch: the whole frame. */
+  int box_y, box_x, box_h, box_w;
+  /* Which of torch's two CPU bilinear kernels the pixels follow.  0: the separable one (lerp along x, then along y) that
+   * F.interpolate runs when output height + width > 128 - every evaluation-branch descriptor, as before the box existed.
+   * T > 0 (the clip's frame count): the four-weight one it runs for smaller outputs, where the frames are the vectorised
+   * dimension: out = w00*p00 + w01*p01 + w10*p10 + w11*p11 with w = products of the two lerp weights, accumulated by fma
+   * from w10*p10 in the order p11, p01, p00 for the frames in whole groups of 8, from w01*p01 in the order p00, p10, p11 for
+   * the T % 8 frames left over.  gava_clip_geometry_box sets it when 2*size <= 128.  The rule was derived from the CPU build
+   * of torch 2.10 on x86 (the same with its AVX2 and AVX512 code paths, any thread count; its scalar no-fma path differs
+   * from both kernels' forms): if tests/test_train_preprocess.py's small-size cases stop matching after a torch upgrade while
+   * the CPU restatement still reproduces the fixtures, this rule is what changed.  The evaluation branch deliberately does
+   * NOT follow it: gava_clip_geometry always sets 0, also where the resized frame is that small, to keep its bits. */
+  int lerp4_frames;
+  /* Frame table: device int[T] with the source frame of every output frame, or NULL = the arithmetic form above.  TSN
+   * sampling (sampling_rate < 0, dataset.py:205-209) has no arithmetic form. */
+  const int* frame_idx;
 } gava_clip_desc;
-/* host helper: the integer / float geometry of dataset.py:124-129,163-186 for one video; 0 on success */
+/* host helper: the integer / float geometry of dataset.py:124-129,163-186 for one video (evaluation branch: whole-frame box,
+ * no frame table); 0 on success */
 int gava_clip_geometry(gava_clip_desc* d, int T, int rate, int size, int first_temporal_view, int first_spatial_view);
+/* host helper for the random-sample branch (dataset.py:93-114 with auto_augment=None): frames idx[0..T) of the video, the box
+ * rows i + [0, h), columns j + [0, w) of each (transform.py:545-577 random_resized_crop) resized to size x size, i.e.
+ * h_st = w_st = 0, scale_h = (float)h / size, scale_w = (float)w / size.  d->frames / n_frames / height / width are set by
+ * the caller.  idx_host: the T indices for checking; idx_dev: the same T ints in device memory, stored as d->frame_idx.
+ * GAVA_EINVAL for an empty box, a box that leaves the frame, or an index outside [0, n_frames): descriptors that pass go to
+ * the device as they are, and the kernels still clamp box and index into the video (wrong pixels at worst, never a wild read). */
+int gava_clip_geometry_box(gava_clip_desc* d, int size, int T, const int* idx_host, const int* idx_dev, int i, int j, int h, int w);
 
 typedef struct {
   const void* A; int64_t lda;       /* h16 [M][lda]                                    */
@@ -474,6 +500,16 @@ typedef struct {
 } gava_preprocess_args;
 int gava_preprocess_clip(const gava_preprocess_args* a, gava_stream_t stream);
 
+/* The same pixels for a whole batch in ONE launch: B descriptors (device array, either branch, videos of different sizes)
+ * -> out fp32 [B][3][T][size][size] by element strides (size*size planes contiguous).  lut = the fp32 [3][256] table of
+ * gava_preprocess_args.lut, required.  Grid = clips x frames x rows; B*T <= 65535.  Same bits as B gava_preprocess_clip calls. */
+typedef struct {
+  const gava_clip_desc* clips; const float* lut;
+  int B, T, size;
+  float* out; int64_t out_stride_b, out_stride_c, out_stride_t;
+} gava_preprocess_clips_args;
+int gava_preprocess_clips(const gava_preprocess_clips_args* a, gava_stream_t stream);
+
 /* The unfold half of ImagePatchEmbed2D (VitaCLIP_vision_encoder_utils.py:31-53: Conv2d(3, D, P, stride P) == patches x
  * W^T) as one HBM-bound pass: the 16-bit patch matrix the patch-embedding GEMM (gava_gemm, EPI_F32_PATCH with A given)
  * then reads by LDS-DMA like any other operand.
@@ -497,7 +533,8 @@ int gava_convert_h16(const float* in, void* out, size_t n, int prec, gava_stream
 
 /* sizeof of every ABI struct as the library was compiled, in the order gemm_args, layernorm_args, attention_args,
  * attention_f32_args, clip_desc, vision_layer, vision_layer8, vision_model, text_layer, text_model, layernorm_bwd_args,
- * attention_bwd_args, vision_saved, preprocess_args, patchify_args.  Writes min(cap, 15) entries, returns 15.  A binding
+ * attention_bwd_args, vision_saved, preprocess_args, patchify_args, preprocess_clips_args.  Writes min(cap, 16) entries,
+ * returns 16.  A binding
  * compares them with its own mirrors at load time (gava_clip_amd/hip.py does): gava_abi_version ties the library to the
  * header, this ties the header to the mirrors. */
 int gava_struct_sizes(size_t* out, int cap);
