@@ -55,6 +55,14 @@ constexpr float LOG2E = 1.4426950408889634f;
 #define GAVA_ATTN_ONESUM 1
 #endif
 
+// Element offset of 16-byte chunk `chunk` of key row `row` of problem (n, h), in K / V (is_main) or in the side matrices
+// (gava::key_row_src: the frame's own rows, then the prompt and summary rows; rows beyond n_keys fetch row 0).
+__device__ __forceinline__ long kv_src_off(const AttnParams& p, int n, int h, int row, int chunk, bool& is_main) {
+  const gava::KeyRowSrc src = gava::key_row_src(n, row, p.n_kmain, p.n_keys, p.n_g, p.T, p.batch);
+  is_main = src.is_main;
+  return src.row * (src.is_main ? p.ld : p.lds) + h * 64 + chunk * 8;
+}
+
 // Stage K and V of problem (n, h) by LDS-DMA: lane l of a 1 KiB piece lands at row (l >> 3), physical chunk (l & 7), so it
 // fetches the logical chunk (l & 7) ^ (row & 6).  Rows beyond n_keys fetch row 0: their scores are masked to -inf, P = 0,
 // and 0 * V must stay finite.  No wait here: the caller owns the s_waitcnt vmcnt and the barrier.
@@ -66,13 +74,8 @@ __device__ __forceinline__ void stage_kv(const AttnParams& p, int n, int h, char
     const int id = tid + it * NTH;
     if (id < KP * 8) {                                                 // wave-uniform: KP * 8 is a multiple of 64
       const int row = id >> 3, chunk = (id & 7) ^ (row & 6);
-      const int rowc = row < p.n_keys ? row : 0;
-      const int sidx = rowc - p.n_kmain;                               // >= 0: side row
-      const long sr = sidx < p.n_g ? sidx
-                    : sidx < p.n_g + p.T ? p.n_g + (long)(n / p.T) * p.T + (sidx - p.n_g)
-                                         : (long)p.n_g + p.batch + n;
-      const bool is_main = rowc < p.n_kmain;
-      const long off = (is_main ? ((long)n * p.n_kmain + rowc) * p.ld : sr * p.lds) + h * 64 + chunk * 8;
+      bool is_main;
+      const long off = kv_src_off(p, n, h, row, chunk, is_main);
       const unsigned short* kb = is_main ? p.k : p.sk;
       const unsigned short* vb = is_main ? p.v : p.sv;
       const int dst = (wave * 64 + it * NTH) * 16;
@@ -84,7 +87,7 @@ __device__ __forceinline__ void stage_kv(const AttnParams& p, int n, int h, char
 
 // One wave stages a whole problem (the persistent kernel's loader wave): 1 KiB pieces of 8 rows each.  Pieces that lie
 // entirely in the main rows advance two pointers by 8 rows; the few pieces with prompt/summary/padding rows take the
-// general row -> source map of stage_kv.
+// general row -> source map (kv_src_off).
 template <int KP>
 __device__ __forceinline__ void stage_kv_one_wave(const AttnParams& p, int n, int h, char* Ks, char* Vs, int lane) {
   const int r8 = lane >> 3, chunk = (lane & 7) ^ (r8 & 6);           // row & 6 == r8 & 6: pieces start at multiples of 8
@@ -100,14 +103,8 @@ __device__ __forceinline__ void stage_kv_one_wave(const AttnParams& p, int n, in
     kp += 8 * p.ld; vp += 8 * p.ld;
   }
   for (; j < KP / 8; ++j) {
-    const int row = j * 8 + r8;
-    const int rowc = row < p.n_keys ? row : 0;
-    const int sidx = rowc - p.n_kmain;                               // >= 0: side row
-    const long sr = sidx < p.n_g ? sidx
-                  : sidx < p.n_g + p.T ? p.n_g + (long)(n / p.T) * p.T + (sidx - p.n_g)
-                                       : (long)p.n_g + p.batch + n;
-    const bool is_main = rowc < p.n_kmain;
-    const long off = (is_main ? ((long)n * p.n_kmain + rowc) * p.ld : sr * p.lds) + h * 64 + chunk * 8;
+    bool is_main;
+    const long off = kv_src_off(p, n, h, j * 8 + r8, chunk, is_main);
     dma16((is_main ? p.k : p.sk) + off, kdst + j * 1024);
     dma16((is_main ? p.v : p.sv) + off, vdst + j * 1024);
   }
@@ -634,17 +631,6 @@ __global__ __launch_bounds__(512, 1) void attention_persist_kernel(const AttnPar
 // it carries the mask.
 constexpr int SKB = 128;   // keys per streamed block: 2 x 2 x 16 KiB of LDS per workgroup, two workgroups per CU
 
-// source of key row `row` of problem n: the frame's own rows, then G global | the clip's T local | the frame's summary row
-__device__ __forceinline__ long kv_src_off(const AttnParams& p, int n, int h, int row, int chunk, bool& is_main) {
-  const int rowc = row < p.n_keys ? row : 0;
-  const int sidx = rowc - p.n_kmain;
-  const long sr = sidx < p.n_g ? sidx
-                : sidx < p.n_g + p.T ? p.n_g + (long)(n / p.T) * p.T + (sidx - p.n_g)
-                                     : (long)p.n_g + p.batch + n;
-  is_main = rowc < p.n_kmain;
-  return (is_main ? ((long)n * p.n_kmain + rowc) * p.ld : sr * p.lds) + h * 64 + chunk * 8;
-}
-
 template <int NTH>
 __device__ __forceinline__ void stage_kv_block(const AttnParams& p, int n, int h, int kb0, char* Ks, char* Vs, int tid, int wave) {
   static_assert(SKB * 8 % NTH == 0, "whole waves per block");
@@ -797,18 +783,12 @@ __global__ __launch_bounds__(NWV * 64, 2) void attention_stream_kernel(const Att
   }
 }
 
-// GAVA_ATTN_STREAM=1 sends every non-causal shape to the streaming kernels (forward and backward; A/B and tests).
-bool stream_forced() {
-  static const bool on = getenv("GAVA_ATTN_STREAM") && getenv("GAVA_ATTN_STREAM")[0] == '1';
-  return on;
-}
-
 template <class P>
 int launch_attn(const AttnParams& p, hipStream_t s) {
   const int n_prob = p.batch * p.heads;
   dim3 grid(n_prob), blk(256);
   const int tiles = (p.n_keys + 15) / 16;
-  if (!p.causal && (tiles > 20 || stream_forced())) {
+  if (!p.causal && (tiles > 20 || gava::stream_forced())) {
     constexpr int NWV = 4;
     const int n_qt = (p.n_q + 15) / 16;
     hipLaunchKernelGGL((attention_stream_kernel<P, NWV>), dim3(n_prob, (n_qt + NWV - 1) / NWV), dim3(NWV * 64), 0, s, p);
@@ -937,6 +917,11 @@ __global__ __launch_bounds__(128) void attention_f32_kernel(const float* __restr
 }
 
 }  // namespace
+
+bool gava::stream_forced() {
+  static const bool on = getenv("GAVA_ATTN_STREAM") && getenv("GAVA_ATTN_STREAM")[0] == '1';
+  return on;
+}
 
 extern "C" int gava_attention_f32(const gava_attention_f32_args* a, gava_stream_t stream) {
   if (!a || !a->q || !a->k || !a->v || !a->out) return GAVA_EINVAL;

@@ -18,6 +18,23 @@ bool gemm_patch_on_persistent(int M, int N, long lda, long ldw);
 int text_embed(const float* emb, const float* pos, const float* ctx, const int* tok, float* X,
                int n_prompts, int L, int W, int n_ctx, hipStream_t s);
 unsigned long long* debug_buffer();   // set by gava_debug_set_buffer; nullptr = stamps off
+// attention.hip: GAVA_ATTN_STREAM=1 sends every non-causal shape to the streaming kernels (forward and backward; A/B and tests)
+bool stream_forced();
+
+// Where key row `row` of frame `frame` lives.  The n_keys keys of a frame are its own n_kmain rows of the main K/V matrix
+// (row = frame * n_kmain + key), then rows of the gathered prompt ("side") matrix: its n_g global rows | the T local rows
+// of the frame's clip | the frame's summary row (the side matrix holds n_g + batch + batch rows).  Rows past n_keys read
+// key 0: their scores are masked, and what stands in for them must be finite.
+struct KeyRowSrc { bool is_main; long row; };
+__device__ __forceinline__ KeyRowSrc key_row_src(int frame, int row, int n_kmain, int n_keys, int n_g, int T, int batch) {
+  const int rowc = row < n_keys ? row : 0;
+  const int sidx = rowc - n_kmain;                                   // >= 0: side row
+  const long sr = sidx < n_g ? sidx
+                : sidx < n_g + T ? n_g + (long)(frame / T) * T + (sidx - n_g)
+                                 : (long)n_g + batch + frame;
+  const bool is_main = rowc < n_kmain;
+  return {is_main, is_main ? (long)frame * n_kmain + rowc : sr};
+}
 
 // MFMA attention backward (attention_bwd.hip), launched by gava_attention_backward (backward.hip)
 struct AttnBwdMfmaParams {
