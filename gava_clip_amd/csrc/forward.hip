@@ -409,7 +409,7 @@ extern "C" int gava_struct_sizes(size_t* out, int cap) {
                       sizeof(gava_clip_desc), sizeof(gava_vision_layer), sizeof(gava_vision_layer8), sizeof(gava_vision_model),
                       sizeof(gava_text_layer), sizeof(gava_text_model), sizeof(gava_layernorm_bwd_args), sizeof(gava_attention_bwd_args),
                       sizeof(gava_vision_saved), sizeof(gava_preprocess_args), sizeof(gava_patchify_args),
-                      sizeof(gava_preprocess_clips_args)};
+                      sizeof(gava_preprocess_clips_args), sizeof(gava_view_scores_args)};
   const int n = (int)(sizeof(v) / sizeof(v[0]));
   for (int i = 0; out && i < n && i < cap; ++i) out[i] = v[i];
   return n;

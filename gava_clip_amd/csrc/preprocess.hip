@@ -3,6 +3,7 @@
 // random-sample branch (:93-114, auto_augment=None), told apart by the descriptor alone (gava_clip_desc).
 // One thread per output pixel and frame, all three channels: the 4 bilinear taps are 4 x 3 adjacent bytes, the
 // three stores are coalesced planes.  HBM-bound: 3 B in (at most 12 touched) and 12 B out per pixel.
+#include <cmath>
 #include "common.h"
 #include "clip_pixel.h"
 
@@ -137,20 +138,22 @@ extern "C" int gava_patchify(const gava_patchify_args* a, gava_stream_t stream) 
   return GAVA_OK;
 }
 
-extern "C" int gava_clip_geometry(gava_clip_desc* d, int T, int rate, int size, int first_temporal_view, int first_spatial_view) {
-  if (!d || d->n_frames <= 0 || d->height <= 0 || d->width <= 0 || T <= 0 || rate <= 0 || size <= 0) return GAVA_EINVAL;
+// The evaluation branch's geometry for one crop: sv in {0, 1, 2} of n_spatial spatial crops (n_spatial == 1: the centred one),
+// temporal start t_st.  Both public helpers below end here, so that the first view is one computation, not two that agree.
+static int clip_geometry_eval(gava_clip_desc* d, int rate, int size, int n_spatial, int sv, int t_st) {
   int new_h, new_w;
   // dataset.py:124-129 (integer arithmetic)
   if (d->height < d->width) { new_w = (int)((long)d->width * size / d->height); new_h = size; }
   else { new_h = (int)((long)d->height * size / d->width); new_w = size; }
   if (new_h < size || new_w < size) return GAVA_EINVAL;   // dataset.py:182 asserts the same
   d->h_st = (new_h - size) / 2; d->w_st = (new_w - size) / 2;
-  if (first_spatial_view) {   // dataset.py:188-199: three crops along the long side, the first at offset 0
+  if (n_spatial == 3) {   // dataset.py:188-199: three crops along the long side, at 0, margin / 2 and margin
     if (new_h != size && new_w != size) return GAVA_EINVAL;   // upstream asserts min side == size
-    d->h_st = 0; d->w_st = 0;
+    const int margin = (new_h > new_w ? new_h : new_w) - size;
+    const int st = sv == 0 ? 0 : sv == 1 ? margin / 2 : margin;
+    d->h_st = new_h > new_w ? st : 0; d->w_st = new_h > new_w ? 0 : st;
   }
-  const int seg = (T - 1) * rate + 1;
-  d->t_st = (d->n_frames > seg && !first_temporal_view) ? (d->n_frames - seg) / 2 : 0;
+  d->t_st = t_st;
   d->rate = rate;
   d->scale_h = (float)d->height / (float)new_h;
   d->scale_w = (float)d->width / (float)new_w;
@@ -158,6 +161,26 @@ extern "C" int gava_clip_geometry(gava_clip_desc* d, int T, int rate, int size, 
   d->lerp4_frames = 0;   // (torch switches kernels at resized height + width <= 128; this branch keeps the separable form it always had)
   d->frame_idx = nullptr;
   return GAVA_OK;
+}
+
+extern "C" int gava_clip_geometry(gava_clip_desc* d, int T, int rate, int size, int first_temporal_view, int first_spatial_view) {
+  if (!d || d->n_frames <= 0 || d->height <= 0 || d->width <= 0 || T <= 0 || rate <= 0 || size <= 0) return GAVA_EINVAL;
+  const int seg = (T - 1) * rate + 1;
+  const int t_st = (d->n_frames > seg && !first_temporal_view) ? (d->n_frames - seg) / 2 : 0;
+  return clip_geometry_eval(d, rate, size, first_spatial_view ? 3 : 1, 0, t_st);
+}
+
+extern "C" int gava_clip_geometry_view(gava_clip_desc* d, int T, int rate, int size, int n_spatial, int n_temporal, int view) {
+  if (!d || d->n_frames <= 0 || d->height <= 0 || d->width <= 0 || T <= 0 || rate <= 0 || size <= 0) return GAVA_EINVAL;
+  if ((n_spatial != 1 && n_spatial != 3) || n_temporal < 1 || view < 0 || (long)view >= (long)n_spatial * n_temporal) return GAVA_EINVAL;
+  const int sv = view / n_temporal, tv = view - sv * n_temporal;
+  // dataset.py:160-175: a video shorter than the segment is padded to it (slide_len 0); the start is Python's
+  // round(slide_len / (n - 1) * i) - the double quotient first, then the product, rounded half to even (nearbyint in the
+  // default rounding mode; lround would round halves away from zero, slide_len * i / (n - 1) is another double)
+  const int seg = (T - 1) * rate + 1;
+  const int slide = d->n_frames > seg ? d->n_frames - seg : 0;
+  const int t_st = n_temporal == 1 ? slide / 2 : (int)nearbyint((double)slide / (double)(n_temporal - 1) * (double)tv);
+  return clip_geometry_eval(d, rate, size, n_spatial, sv, t_st);
 }
 
 extern "C" int gava_clip_geometry_box(gava_clip_desc* d, int size, int T, const int* idx_host, const int* idx_dev, int i, int j,

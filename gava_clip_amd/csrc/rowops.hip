@@ -325,7 +325,92 @@ __global__ __launch_bounds__(256) void row_stats_kernel(const float2* part, int 
   stats[r0 + r] = make_float2(mean, 1.0f / sqrtf(var + 1e-5f));
 }
 
+// ---- multi-view score fusion (gava_view_scores): scores[b] = mean over the V views of softmax over the C classes, fp32.
+// One workgroup per video.  Views map onto waves: a wave reduces the max and the sum of exp over the classes of its view (lanes
+// stride the classes; xor butterflies, so every lane holds the same bits) and leaves (max, 1 / sum) in LDS.  Classes then map onto
+// threads: each adds the V terms exp(x - max_v) / sum_v of its class in view order.  Nothing depends on which wave ran first.
+// VS_CHUNK views share the LDS table at a time; a video with more views carries the running sums of its classes through
+// `scores` (read and written by the same thread).  The work is a few KB per video: the cost of the call is its launch.
+constexpr int VS_THREADS = 512, VS_WAVES = VS_THREADS / 64, VS_CHUNK = 64;
+struct ViewScoreParams {
+  const float* logits; long ld_video, ld_view;
+  int V, C;
+  float* scores; int* top1;
+};
+
+static __device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// (value, index) a beats b: the larger score, the lower class on equal scores
+static __device__ __forceinline__ bool score_beats(float va, int ia, float vb, int ib) { return va > vb || (va == vb && ia < ib); }
+
+__global__ __launch_bounds__(VS_THREADS) void view_scores_kernel(const ViewScoreParams p) {
+  __shared__ float2 stat[VS_CHUNK];            // (max, 1 / sum of exp) of each view of the chunk
+  __shared__ float best_v[VS_WAVES];
+  __shared__ int best_i[VS_WAVES];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float* x = p.logits + (long)blockIdx.x * p.ld_video;
+  float* out = p.scores + (long)blockIdx.x * p.C;
+  float bv = -1.f;                             // scores are >= 0: any class beats the start value
+  int bi = 0x7fffffff;
+  for (int v0 = 0; v0 < p.V; v0 += VS_CHUNK) {
+    const int nv = min(VS_CHUNK, p.V - v0);
+    for (int v = wave; v < nv; v += VS_WAVES) {
+      const float* r = x + (long)(v0 + v) * p.ld_view;
+      float m = -INFINITY;
+      for (int c = lane; c < p.C; c += 64) m = fmaxf(m, r[c]);
+      m = wave_max(m);
+      float s = 0.f;
+      for (int c = lane; c < p.C; c += 64) s += expf(r[c] - m);
+      s = wave_sum(s);
+      if (lane == 0) stat[v] = make_float2(m, 1.0f / s);
+    }
+    __syncthreads();
+    const bool first = v0 == 0, last = v0 + nv == p.V;
+    for (int c = threadIdx.x; c < p.C; c += VS_THREADS) {
+      float acc = first ? 0.f : out[c];
+      for (int v = 0; v < nv; ++v) {
+        const float2 st = stat[v];
+        acc += expf(x[(long)(v0 + v) * p.ld_view + c] - st.x) * st.y;
+      }
+      if (last) {
+        acc /= (float)p.V;
+        if (acc > bv) { bv = acc; bi = c; }    // c ascends within a thread: strictly greater keeps the lowest class
+      }
+      out[c] = acc;
+    }
+    __syncthreads();                           // the next chunk overwrites stat
+  }
+  if (!p.top1) return;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(bv, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (score_beats(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+  }
+  if (lane == 0) { best_v[wave] = bv; best_i[wave] = bi; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < VS_WAVES; ++w)
+      if (score_beats(best_v[w], best_i[w], bv, bi)) { bv = best_v[w]; bi = best_i[w]; }
+    p.top1[blockIdx.x] = bi < p.C ? bi : 0;    // (no class beat the start value: NaN logits)
+  }
+}
+
 }  // namespace
+
+extern "C" int gava_view_scores(const gava_view_scores_args* a, gava_stream_t stream) {
+  if (!a || a->B < 0 || a->V <= 0 || a->C <= 0) return GAVA_EINVAL;
+  if (a->B == 0) return GAVA_OK;
+  if (!a->logits || !a->scores) return GAVA_EINVAL;
+  ViewScoreParams p{a->logits, (long)a->ld_video, (long)a->ld_view, a->V, a->C, a->scores, a->top1};
+  hipLaunchKernelGGL(view_scores_kernel, dim3(a->B), dim3(VS_THREADS), 0, (hipStream_t)stream, p);
+  GAVA_CHECK_LAUNCH();
+  return GAVA_OK;
+}
 
 extern "C" int gava_row_stats(const float* rowsum, int slots, int D, int rows, float* stats, gava_stream_t stream) {
   if (!rowsum || !stats || slots <= 0 || slots > RS_MAX_SLOTS || D <= 0 || rows <= 0) return GAVA_EINVAL;

@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("GAVA_HIP_LIB") or os.path.join(_HERE, "libgava_hip.so
 PREC_F16, PREC_BF16 = 0, 1
 KERNEL_AUTO, KERNEL_256, KERNEL_PAIR, KERNEL_PP = 0, 3, 4, 5     # gava_gemm_args.kernel
 EPI_H16, EPI_H16_QGELU, EPI_F32, EPI_F32_PATCH, EPI_H16_QGELU_BWD = 0, 1, 2, 3, 4
+MAX_GRID_FRAMES = 65535      # clips x frames one gava_preprocess_clips / gava_patchify launch covers (its grid's z extent)
 PREC_NAMES = {"fp16": PREC_F16, "f16": PREC_F16, "bf16": PREC_BF16}
 PREC_TORCH = {PREC_F16: torch.float16, PREC_BF16: torch.bfloat16}
 
@@ -24,7 +25,7 @@ EXPORTS = ["gava_abi_version", "gava_gemm", "gava_layernorm", "gava_attention",
            "gava_text_forward_train", "gava_vision_forward_train", "gava_attention_backward_workspace_bytes", "gava_vision_forward_keep", "gava_row_stats",
            "gava_probe_fc1_enable", "gava_probe_fc1_read", "gava_clip_geometry", "gava_patchify", "gava_attention_f32",
            "gava_gemm_aligned_walk", "gava_vision_pair_stream", "gava_struct_sizes", "gava_clip_geometry_box",
-           "gava_preprocess_clips"]
+           "gava_preprocess_clips", "gava_clip_geometry_view", "gava_view_scores"]
 
 _vp, _fp, _ip = C.c_void_p, C.c_void_p, C.c_void_p  # all device pointers travel as void*
 
@@ -128,6 +129,11 @@ class PreprocessClipsArgs(C.Structure):
                 ("out", _fp), ("out_stride_b", C.c_int64), ("out_stride_c", C.c_int64), ("out_stride_t", C.c_int64)]
 
 
+class ViewScoresArgs(C.Structure):
+    _fields_ = [("logits", _fp), ("ld_video", C.c_int64), ("ld_view", C.c_int64),
+                ("B", C.c_int), ("V", C.c_int), ("C", C.c_int), ("scores", _fp), ("top1", _ip)]
+
+
 class PatchifyArgs(C.Structure):
     _fields_ = [("x", _fp), ("clips", _vp), ("clip_lut", _fp),
                 ("B", C.c_int), ("T", C.c_int), ("size", C.c_int), ("patch", C.c_int), ("prec", C.c_int),
@@ -228,6 +234,8 @@ def load():
     lib.gava_clip_geometry_box.argtypes = [C.POINTER(ClipDesc), C.c_int, C.c_int, C.POINTER(C.c_int), _ip] + [C.c_int] * 4
     lib.gava_clip_geometry_box.restype = C.c_int
     lib.gava_preprocess_clips.argtypes, lib.gava_preprocess_clips.restype = [C.POINTER(PreprocessClipsArgs), _vp], C.c_int
+    lib.gava_clip_geometry_view.argtypes, lib.gava_clip_geometry_view.restype = [C.POINTER(ClipDesc)] + [C.c_int] * 6, C.c_int
+    lib.gava_view_scores.argtypes, lib.gava_view_scores.restype = [C.POINTER(ViewScoresArgs), _vp], C.c_int
     lib.gava_gemm_aligned_walk.argtypes, lib.gava_gemm_aligned_walk.restype = [C.c_int, C.c_int, C.c_int], C.c_int
     lib.gava_probe_fc1_enable.argtypes = [C.c_int]
     lib.gava_probe_fc1_read.argtypes = [C.POINTER(C.c_float), C.c_int]
@@ -242,7 +250,8 @@ def load():
     lib.gava_vision_pair_stream.argtypes, lib.gava_vision_pair_stream.restype = [C.POINTER(VisionModel)], C.c_int
     # the header the library was compiled from against the mirrors above (gava_abi_version ties library and header)
     mirrors = [GemmArgs, LayerNormArgs, AttentionArgs, AttentionF32Args, ClipDesc, VisionLayer, VisionLayer8, VisionModel, TextLayer,
-               TextModel, LayerNormBwdArgs, AttentionBwdArgs, VisionSaved, PreprocessArgs, PatchifyArgs, PreprocessClipsArgs]
+               TextModel, LayerNormBwdArgs, AttentionBwdArgs, VisionSaved, PreprocessArgs, PatchifyArgs, PreprocessClipsArgs,
+               ViewScoresArgs]
     sizes = (C.c_size_t * len(mirrors))()
     lib.gava_struct_sizes.argtypes, lib.gava_struct_sizes.restype = [C.POINTER(C.c_size_t), C.c_int], C.c_int
     if lib.gava_struct_sizes(sizes, len(mirrors)) != len(mirrors):
@@ -506,3 +515,41 @@ def clip_descriptors_box(videos, draws, *, size):
               "gava_clip_geometry_box")
     host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
     return host.to(dev), list(videos) + [tables]
+
+
+def clip_descriptors_views(videos, *, T, rate, size, n_spatial, n_temporal):
+    """Every evaluation crop of every video (dataset.py:135-136 builds n_spatial x n_temporal of them): -> (uint8 device tensor
+    holding B*V gava_clip_desc, video-major with a video's V views in upstream's order view = sv * n_temporal + tv; keep-alive
+    list; host int32 array [B*V, 3] with each clip's (t_st, h_st, w_st)).  Geometry by the library (gava_clip_geometry_view)."""
+    import numpy as np
+    lib = load()
+    V = n_spatial * n_temporal
+    arr = (ClipDesc * (len(videos) * V))()
+    for b, v in enumerate(videos):
+        assert v.is_cuda and v.dtype == torch.uint8 and v.dim() == 4 and v.shape[-1] == 3 and v.is_contiguous()
+        for k in range(V):
+            d = arr[b * V + k]
+            d.frames, d.n_frames, d.height, d.width = ptr(v), v.shape[0], v.shape[1], v.shape[2]
+            check(lib.gava_clip_geometry_view(C.byref(d), T, rate, size, n_spatial, n_temporal, k), "gava_clip_geometry_view")
+    raw = np.frombuffer(bytes(arr), dtype=np.uint8).reshape(len(arr), C.sizeof(ClipDesc))
+    first = ClipDesc.t_st.offset
+    assert ClipDesc.h_st.offset == first + 8 and ClipDesc.w_st.offset == first + 12
+    geom = raw[:, first:first + 16].copy().view(np.int32)[:, [0, 2, 3]]
+    return torch.from_numpy(raw.copy()).reshape(-1).to(videos[0].device), list(videos), geom
+
+
+def view_scores(logits):
+    """Multi-view score fusion (gava_view_scores): logits = fp32 device tensor [B, V, C] whose last dimension is contiguous (any
+    video / view strides) -> (scores fp32 [B, C] = mean over the views of softmax over the classes, top1 int32 [B] = its argmax,
+    the lowest class on ties).  One launch, no sync."""
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 3, "logits must be a device fp32 [B, V, C] tensor"
+    B, V, Cn = logits.shape
+    assert Cn == 1 or logits.stride(2) == 1, "the class dimension must be contiguous"
+    scores = torch.empty(B, Cn, dtype=torch.float32, device=logits.device)
+    top1 = torch.empty(B, dtype=torch.int32, device=logits.device)
+    a = ViewScoresArgs()
+    a.logits, a.ld_video, a.ld_view = ptr(logits), logits.stride(0), logits.stride(1)
+    a.B, a.V, a.C, a.scores, a.top1 = B, V, Cn, ptr(scores), ptr(top1)
+    with torch.cuda.device(logits.device):
+        check(load().gava_view_scores(C.byref(a), stream_ptr(logits.device)), "gava_view_scores")
+    return scores, top1

@@ -1057,6 +1057,64 @@ class VitaCLIP(nn.Module, _HipHost):
             # (`keep` - the contiguous videos and the frame tables - lives until the patch embedding is enqueued, no longer)
             return self._forward_impl(desc, memory, video_nte, desc_wise, clips=clips)
 
+    def forward_views(self, videos, preprocessor, max_clips=None):
+        """Multi-view evaluation: every one of the preprocessor's V = num_spatial_views x num_temporal_views crops of every
+        video (video_dataset/dataset.py:135-136,160-199; the views dataloader.py:31-34 asks for and dataset.py:137-139 drops)
+        through the towers, and the fused view scores of evaluation/evaluate.py:283 - softmax over the classes per view,
+        mean over a video's views.  `videos` as for forward_frames, `preprocessor` a ClipPreprocessor.
+        -> (scores fp32 [B, C], logits fp32 [B, V, C], top1 int32 [B] = argmax of scores, lowest class on ties).
+
+        Evaluation only: call it under torch.no_grad() on a model in eval() mode.  The patch embedding reads the uint8
+        frames of each crop itself (as forward_frames does); clips go through in chunks of whole videos, by default the
+        most videos whose clips x frames fit one launch's grid (65535 frames).  `max_clips` lowers that - one launch's
+        workspace grows with its clip count - rounded down to a multiple of V and never below V.  The text features are
+        cached for the duration of the call (cache_text_features is restored afterwards), so the text tower runs once, not
+        once per chunk.  The call ends with one gava_view_scores launch and never waits for the device.
+
+        Several ranks: each rank passes its own videos (the same number on every rank); the all-gather inside the forward
+        returns every rank's clips in rank order, so logits is [B_global, V, C] and scores / top1 cover the global batch,
+        rank-major, as forward()'s logits do."""
+        from .preprocess import ClipPreprocessor
+        if torch.is_grad_enabled() or self.training:
+            raise hip.GavaError("forward_views is the evaluation path: call it under torch.no_grad() on a model in eval() mode")
+        pre = preprocessor
+        if not isinstance(pre, ClipPreprocessor):
+            raise hip.GavaError("forward_views takes a ClipPreprocessor (the evaluation branch builds the views; the random-sample "
+                                "branch has none)")
+        assert pre.spatial_size == self._shape["size"], "the preprocessor's crop size must be the model's input size"
+        if not videos:
+            raise ValueError("forward_views needs at least one video")
+        B, V, T = len(videos), pre.num_views, pre.num_frames
+        fit = hip.MAX_GRID_FRAMES // T // V * V
+        if fit < V:
+            raise hip.GavaError(f"one video's {V} views x {T} frames are past the {hip.MAX_GRID_FRAMES} frames one launch covers")
+        step = fit if max_clips is None else min(fit, max(int(max_clips) // V * V, V))
+        dev = videos[0].device
+        cached = self.cache_text_features
+        self.cache_text_features = True
+        try:
+            with torch.cuda.device(dev):
+                pre.check(videos)
+                desc, keep, _ = pre.view_descriptors([v.contiguous() for v in videos])
+                stride = desc.numel() // (B * V)
+                logits = None
+                for i in range(0, B * V, step):
+                    n = min(step, B * V - i)
+                    clips = (desc[i * stride:(i + n) * stride], n, T, pre.lut(dev), dev)
+                    lg = self._forward_impl(clips[0], None, None, False, clips=clips)[0]
+                    if n == B * V:
+                        logits = lg.view(-1, V, lg.shape[-1])
+                        break
+                    world = lg.shape[0] // n               # ranks whose clips the forward gathered (1 without a process group)
+                    if logits is None:
+                        logits = torch.empty(world * B, V, lg.shape[-1], dtype=torch.float32, device=dev)
+                    logits.view(world, B, V, -1)[:, i // V:(i + n) // V] = lg.view(world, n // V, V, -1)
+                self.last["local_batch"] = B
+                scores, top1 = hip.view_scores(logits)
+        finally:
+            self.cache_text_features = cached
+        return scores, logits, top1
+
     def _forward_impl(self, x, memory, video_nte, desc_wise, clips=None):
         lib = hip.load()
         if clips is not None:

@@ -37,7 +37,8 @@ class ClipPreprocessor:
         if num_spatial_views not in (1, 3):
             raise NotImplementedError()          # dataset.py:201-202
         # upstream builds all num_spatial_views x num_temporal_views crops but returns only the first one
-        # (`frames = frames[0]`, dataset.py:134-139): the top/left spatial crop and the temporal crop starting at frame 0
+        # (`frames = frames[0]`, dataset.py:134-139): the top/left spatial crop and the temporal crop starting at frame 0.
+        # __call__, batch and descriptors serve that one; view_descriptors / batch_views serve all of them.
         self.num_spatial_views, self.num_temporal_views = num_spatial_views, num_temporal_views
         self.num_frames, self.sampling_rate, self.spatial_size = num_frames, sampling_rate, spatial_size
         self.mean = tuple(float(v) for v in torch.as_tensor(mean).flatten().tolist())
@@ -88,6 +89,35 @@ class ClipPreprocessor:
         """list of uint8 [n_i, H_i, W_i, 3] -> fp32 [B, 3, T, S, S]: one launch for the batch (gava_preprocess_clips), videos
         of different sizes included; the same bits as calling the preprocessor clip by clip."""
         return _batch(self, videos, self.descriptors)
+
+
+    @property
+    def num_views(self):
+        """crops per video that upstream builds (dataset.py:135-136)"""
+        return self.num_spatial_views * self.num_temporal_views
+
+    def view_descriptors(self, videos):
+        """-> (device array of B * num_views gava_clip_desc, keep-alive list, host int32 [B * num_views, 3] of (t_st, h_st,
+        w_st)): every view of every checked video, video-major, a video's views in upstream's order (spatial-major)."""
+        return hip.clip_descriptors_views(videos, T=self.num_frames, rate=self.sampling_rate, size=self.spatial_size,
+                                          n_spatial=self.num_spatial_views, n_temporal=self.num_temporal_views)
+
+    def batch_views(self, videos):
+        """list of uint8 [n_i, H_i, W_i, 3] -> fp32 [B, V, 3, T, S, S], V = num_views: every crop upstream builds, in its order.
+        One gava_preprocess_clips launch, or several where B * V * T passes that kernel's grid bound of 65535 frames."""
+        T, S, V = self.num_frames, self.spatial_size, self.num_views
+        dev = videos[0].device
+        with torch.cuda.device(dev):
+            self.check(videos)
+            desc, keep, _ = self.view_descriptors([v.contiguous() for v in videos])
+            x = torch.empty(len(videos), V, 3, T, S, S, dtype=torch.float32, device=dev)
+            flat, stride = x.view(-1, 3, T, S, S), desc.numel() // (len(videos) * V)
+            step = hip.MAX_GRID_FRAMES // T
+            if step < 1:
+                raise hip.GavaError(f"num_frames = {T} is past the {hip.MAX_GRID_FRAMES} frames one launch covers")
+            for i in range(0, flat.shape[0], step):
+                hip.preprocess_clips(desc[i * stride:(i + step) * stride], flat[i:i + step], T=T, size=S, lut=self.lut(dev))
+        return x
 
 
 def _batch(pre, videos, descriptors):

@@ -96,6 +96,17 @@ typedef struct {
 /* host helper: the integer / float geometry of dataset.py:124-129,163-186 for one video (evaluation branch: whole-frame box,
  * no frame table); 0 on success */
 int gava_clip_geometry(gava_clip_desc* d, int T, int rate, int size, int first_temporal_view, int first_spatial_view);
+/* host helper: the geometry of ONE of the n_spatial x n_temporal evaluation crops of a video (dataset.py:135-136 builds them
+ * all), view = sv * n_temporal + tv in the order of upstream's list (spatial-major).  d->frames / n_frames / height / width are
+ * set by the caller, as for gava_clip_geometry.
+ *   temporal (:160-175)  slide_len = max(n_frames - ((T-1)*rate + 1), 0); t_st = slide_len / 2 when n_temporal == 1, else
+ *                        Python's round(slide_len / (n_temporal-1) * tv): the double quotient first, then the product, rounded
+ *                        half to even.  frame(t) = min(t_st + t*rate, n_frames-1) supplies upstream's last-frame padding.
+ *   spatial (:178-199)   n_spatial == 1: the centred crop; n_spatial == 3: offsets (0, margin/2, margin) along the longer
+ *                        resized side, margin = max(new_h, new_w) - size, 0 along the other (a square frame: three equal views).
+ * GAVA_EINVAL for any other n_spatial, n_temporal < 1 or view outside [0, n_spatial*n_temporal).  View 0 is, byte for byte, what
+ * gava_clip_geometry writes with first_temporal_view = n_temporal > 1 and first_spatial_view = n_spatial == 3. */
+int gava_clip_geometry_view(gava_clip_desc* d, int T, int rate, int size, int n_spatial, int n_temporal, int view);
 /* host helper for the random-sample branch (dataset.py:93-114 with auto_augment=None): frames idx[0..T) of the video, the box
  * rows i + [0, h), columns j + [0, w) of each (transform.py:545-577 random_resized_crop) resized to size x size, i.e.
  * h_st = w_st = 0, scale_h = (float)h / size, scale_w = (float)w / size.  d->frames / n_frames / height / width are set by
@@ -382,6 +393,20 @@ int gava_similarity_head(const float* video, const float* text, const float* log
                          const float* logit_bias, int B, int C, int n_kv, int E, float* logits,
                          float* text_features, float* video_norm, gava_stream_t stream);
 
+/* Multi-view score fusion (evaluation/evaluate.py:275-288 with every view kept: softmax over the classes per view, :283, then
+ * the mean over the num_spatial_views x num_temporal_views crops of a video that the upstream recipe takes).  All fp32:
+ *   scores[b][c] = 1/V * sum_v exp(logit(b,v,c) - max_c' logit(b,v,c')) / sum_c' exp(logit(b,v,c') - max),
+ * one launch for the batch, one workgroup per video: a wave per view reduces max and sum over the classes (lanes stride the
+ * classes), the per-view (max, 1/sum) pairs meet in LDS, and every class then adds its V terms in view order - the result does
+ * not depend on timing (no atomics).  Any V >= 1 and C >= 1; B == 0 succeeds without a launch. */
+typedef struct {
+  const float* logits; int64_t ld_video, ld_view;   /* logit(b,v,c) = logits[b*ld_video + v*ld_view + c] */
+  int B, V, C;
+  float* scores;      /* fp32 [B][C] contiguous: mean over the V views of softmax over the C classes */
+  int* top1;          /* optional int32 [B]: argmax_c scores[b][c], lowest index on ties */
+} gava_view_scores_args;
+int gava_view_scores(const gava_view_scores_args* a, gava_stream_t stream);
+
 /* ---- Backward of the trainable subset (training/train.py:441-490) --------------------------
  * Every transformer weight of the reference is frozen (VitaCLIP_model.py:230-239): the gradient only has to flow
  * THROUGH the GEMMs to the prompt parameters.  dgrad is gava_gemm on a transposed weight copy
@@ -533,8 +558,8 @@ int gava_convert_h16(const float* in, void* out, size_t n, int prec, gava_stream
 
 /* sizeof of every ABI struct as the library was compiled, in the order gemm_args, layernorm_args, attention_args,
  * attention_f32_args, clip_desc, vision_layer, vision_layer8, vision_model, text_layer, text_model, layernorm_bwd_args,
- * attention_bwd_args, vision_saved, preprocess_args, patchify_args, preprocess_clips_args.  Writes min(cap, 16) entries,
- * returns 16.  A binding
+ * attention_bwd_args, vision_saved, preprocess_args, patchify_args, preprocess_clips_args, view_scores_args.  Writes
+ * min(cap, 17) entries, returns 17.  A binding
  * compares them with its own mirrors at load time (gava_clip_amd/hip.py does): gava_abi_version ties the library to the
  * header, this ties the header to the mirrors. */
 int gava_struct_sizes(size_t* out, int cap);
