@@ -10,4 +10,7 @@ def __getattr__(name):  # lazy: importing the package must not need torch/HIP
     if name == "VitaCLIP":
         from .model import VitaCLIP
         return VitaCLIP
+    if name == "TrainCriterion":
+        from .training import TrainCriterion
+        return TrainCriterion
     raise AttributeError(name)

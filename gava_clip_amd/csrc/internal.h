@@ -17,6 +17,11 @@ bool gemm_takes_pair(int M, int N, int K, long lda, long ldw);
 bool gemm_patch_on_persistent(int M, int N, long lda, long ldw);
 int text_embed(const float* emb, const float* pos, const float* ctx, const int* tok, float* X,
                int n_prompts, int L, int W, int n_ctx, hipStream_t s);
+// rowops.hip: l2norm_rows, class_mean (by class_offsets), logits_mfma, text_feature - the launches of gava_similarity_head, keeping
+// what gava_train_head_backward reuses (unit rows, 1 / |row|, the class means before their re-normalisation)
+int train_head_forward(const float* video, const float* text, const int* offsets, const float* logit_scale, const float* logit_bias,
+                       int B, int C, int P, int E, float* logits, float* text_features, float* video_norm, float* video_inv,
+                       float* text_norm, float* text_inv, float* class_mean, hipStream_t s);
 unsigned long long* debug_buffer();   // set by gava_debug_set_buffer; nullptr = stamps off
 // attention.hip: GAVA_ATTN_STREAM=1 sends every non-causal shape to the streaming kernels (forward and backward; A/B and tests)
 bool stream_forced();

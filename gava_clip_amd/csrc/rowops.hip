@@ -233,7 +233,8 @@ __global__ void convert_kernel(const float* in, unsigned short* out, size_t n) {
 }
 
 // ---- similarity head, all fp32 (VitaCLIP_model.py:255,287-293).  One wave per output.
-__global__ void l2norm_rows_kernel(const float* in, float* out, int rows, int E) {
+// inv_out (training head only): 1 / |row|, which the backward of the normalisation divides by
+__global__ void l2norm_rows_kernel(const float* in, float* out, int rows, int E, float* inv_out) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -241,6 +242,7 @@ __global__ void l2norm_rows_kernel(const float* in, float* out, int rows, int E)
   for (int c = lane; c < E; c += 64) { const float v = in[(long)row * E + c]; s += v * v; }
   const float inv = 1.0f / sqrtf(wave_sum(s));
   for (int c = lane; c < E; c += 64) out[(long)row * E + c] = in[(long)row * E + c] * inv;
+  if (inv_out && lane == 0) inv_out[row] = inv;
 }
 
 // logits = exp(logit_scale) * V T^T (+ bias) as ONE fp32 MFMA GEMM: v_mfma_f32_16x16x4_f32 is bit-for-bit an
@@ -270,19 +272,32 @@ __global__ __launch_bounds__(64) void logits_mfma_kernel(const float* vn, const 
 
 // m[c] = mean_k normalise(t[c][k]): the class mean of the unit prompt features.  By linearity
 // mean_k <v, normalise(t_ck)> = <v, m_c>, so the logits need one GEMM against m (VitaCLIP_model.py:288-289).
-__global__ void class_mean_kernel(const float* t, float* m, int C, int n_kv, int E) {
+// Training head (gava_train_head): `offsets` [C+1] names the prompts of class c as rows offsets[c] .. offsets[c+1] of the P rows
+// of t (n_kv is then unused; a class may have its own count), and the unit rows and 1 / |row| are kept in tn_out / inv_out for the
+// backward.  The arithmetic of m is the same statement either way: equal counts give the bits of the n_kv form.
+__global__ void class_mean_kernel(const float* t, float* m, int C, int n_kv, int E, const int* offsets, int P,
+                                  float* tn_out, float* inv_out) {
   const int lane = threadIdx.x & 63;
   const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (c >= C) return;
+  long first = (long)c * n_kv;
+  if (offsets) {       // a descriptor that disagrees with P must not send the reads past the matrix
+    const int lo = min(max(offsets[c], 0), P), hi = min(max(offsets[c + 1], lo), P);
+    first = lo; n_kv = hi - lo;
+  }
   for (int e = lane; e < E; e += 64) m[(long)c * E + e] = 0.f;
   for (int k = 0; k < n_kv; ++k) {
-    const float* r = t + ((long)c * n_kv + k) * E;
+    const float* r = t + (first + k) * E;
     float s = 0.f;
     for (int e = lane; e < E; e += 64) s += r[e] * r[e];
     const float inv = 1.0f / sqrtf(wave_sum(s));
     for (int e = lane; e < E; e += 64) m[(long)c * E + e] += r[e] * inv;
+    if (tn_out) {
+      for (int e = lane; e < E; e += 64) tn_out[(first + k) * E + e] = r[e] * inv;
+      if (lane == 0) inv_out[first + k] = inv;
+    }
   }
-  for (int e = lane; e < E; e += 64) m[(long)c * E + e] /= (float)n_kv;
+  for (int e = lane; e < E; e += 64) m[(long)c * E + e] /= (float)max(n_kv, 1);      // (a class without prompts: zeros)
 }
 
 // text_features[c] = normalise(mean_k tn[c][k])
@@ -463,9 +478,10 @@ extern "C" int gava_similarity_head(const float* video, const float* text, const
   if (!video || !text || !logit_scale || !logits || !text_features || !video_norm) return GAVA_EINVAL;
   if (B <= 0 || C <= 0 || E <= 0 || n_kv <= 0 || E % 4) return GAVA_EINVAL;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(l2norm_rows_kernel, dim3((B + 3) / 4), dim3(256), 0, s, video, video_norm, B, E);
-  if (n_kv == 1) hipLaunchKernelGGL(l2norm_rows_kernel, dim3((C + 3) / 4), dim3(256), 0, s, text, text_features, C, E);
-  else hipLaunchKernelGGL(class_mean_kernel, dim3((C + 3) / 4), dim3(256), 0, s, text, text_features, C, n_kv, E);
+  hipLaunchKernelGGL(l2norm_rows_kernel, dim3((B + 3) / 4), dim3(256), 0, s, video, video_norm, B, E, (float*)nullptr);
+  if (n_kv == 1) hipLaunchKernelGGL(l2norm_rows_kernel, dim3((C + 3) / 4), dim3(256), 0, s, text, text_features, C, E, (float*)nullptr);
+  else hipLaunchKernelGGL(class_mean_kernel, dim3((C + 3) / 4), dim3(256), 0, s, text, text_features, C, n_kv, E,
+                          (const int*)nullptr, 0, (float*)nullptr, (float*)nullptr);
   hipLaunchKernelGGL(logits_mfma_kernel, dim3(((B + 15) / 16) * ((C + 15) / 16)), dim3(64), 0, s, video_norm,
                      text_features, logit_scale, logit_bias, B, C, E, logits);
   hipLaunchKernelGGL(text_feature_kernel, dim3((C + 3) / 4), dim3(256), 0, s, text_features, text_features, C, 1, E);
@@ -525,6 +541,19 @@ int join_rows(const void* hi, const void* lo, long in_stride, float* out, long o
   else if (prec == GAVA_PREC_BF16)
     hipLaunchKernelGGL(join_rows_kernel<PrecBF16>, grid, block, 0, s, (const unsigned short*)hi, (const unsigned short*)lo, in_stride, out, out_stride, rows, D);
   else return GAVA_EINVAL;
+  GAVA_CHECK_LAUNCH();
+  return GAVA_OK;
+}
+
+// forward of the training head (train_head.hip): the similarity head's own kernels, so that both heads give the same bits
+int train_head_forward(const float* video, const float* text, const int* offsets, const float* logit_scale, const float* logit_bias,
+                       int B, int C, int P, int E, float* logits, float* text_features, float* video_norm, float* video_inv,
+                       float* text_norm, float* text_inv, float* class_mean, hipStream_t s) {
+  hipLaunchKernelGGL(l2norm_rows_kernel, dim3((B + 3) / 4), dim3(256), 0, s, video, video_norm, B, E, video_inv);
+  hipLaunchKernelGGL(class_mean_kernel, dim3((C + 3) / 4), dim3(256), 0, s, text, class_mean, C, 0, E, offsets, P, text_norm, text_inv);
+  hipLaunchKernelGGL(logits_mfma_kernel, dim3(((B + 15) / 16) * ((C + 15) / 16)), dim3(64), 0, s, video_norm, class_mean,
+                     logit_scale, logit_bias, B, C, E, logits);
+  hipLaunchKernelGGL(text_feature_kernel, dim3((C + 3) / 4), dim3(256), 0, s, class_mean, text_features, C, 1, E);
   GAVA_CHECK_LAUNCH();
   return GAVA_OK;
 }

@@ -25,7 +25,9 @@ EXPORTS = ["gava_abi_version", "gava_gemm", "gava_layernorm", "gava_attention",
            "gava_text_forward_train", "gava_vision_forward_train", "gava_attention_backward_workspace_bytes", "gava_vision_forward_keep", "gava_row_stats",
            "gava_probe_fc1_enable", "gava_probe_fc1_read", "gava_clip_geometry", "gava_patchify", "gava_attention_f32",
            "gava_gemm_aligned_walk", "gava_vision_pair_stream", "gava_struct_sizes", "gava_clip_geometry_box",
-           "gava_preprocess_clips", "gava_clip_geometry_view", "gava_view_scores"]
+           "gava_preprocess_clips", "gava_clip_geometry_view", "gava_view_scores",
+           "gava_train_criterion", "gava_train_criterion_backward", "gava_train_head", "gava_train_head_backward",
+           "gava_train_struct_sizes"]
 
 _vp, _fp, _ip = C.c_void_p, C.c_void_p, C.c_void_p  # all device pointers travel as void*
 
@@ -132,6 +134,23 @@ class PreprocessClipsArgs(C.Structure):
 class ViewScoresArgs(C.Structure):
     _fields_ = [("logits", _fp), ("ld_video", C.c_int64), ("ld_view", C.c_int64),
                 ("B", C.c_int), ("V", C.c_int), ("C", C.c_int), ("scores", _fp), ("top1", _ip)]
+
+
+class TrainCriterionArgs(C.Structure):
+    _fields_ = [("logits", _fp), ("ld_logits", C.c_int64), ("labels", _ip),
+                ("B", C.c_int), ("C", C.c_int), ("weighted", C.c_int),
+                ("alpha", C.c_float), ("gamma", C.c_float), ("beta", C.c_float), ("scale", C.c_float),
+                ("loss", _fp), ("per_sample", _fp), ("weight", _fp), ("top1", _ip), ("hits", _ip), ("conf", _ip),
+                ("saved", _fp), ("grad_loss", _fp), ("dlogits", _fp), ("ld_dlogits", C.c_int64)]
+
+
+class TrainHeadArgs(C.Structure):
+    _fields_ = [("video", _fp), ("text", _fp), ("class_offsets", _ip), ("logit_scale", _fp), ("logit_bias", _fp),
+                ("B", C.c_int), ("C", C.c_int), ("P", C.c_int), ("E", C.c_int),
+                ("logits", _fp), ("text_features", _fp),
+                ("video_norm", _fp), ("video_inv", _fp), ("text_norm", _fp), ("text_inv", _fp), ("class_mean", _fp),
+                ("dlogits", _fp), ("dtext_features", _fp),
+                ("dvideo", _fp), ("dtext", _fp), ("dlogit_scale", _fp), ("dlogit_bias", _fp), ("workspace", _fp)]
 
 
 class PatchifyArgs(C.Structure):
@@ -257,6 +276,19 @@ def load():
     if lib.gava_struct_sizes(sizes, len(mirrors)) != len(mirrors):
         raise GavaError("libgava_hip.so and gava_clip_amd/hip.py disagree on the number of ABI structs")
     for cls, sz in zip(mirrors, sizes):
+        if C.sizeof(cls) != sz:
+            raise GavaError(f"ctypes mirror {cls.__name__} is {C.sizeof(cls)} bytes, the library's struct {sz}: gava_clip_amd/hip.py is out of "
+                            f"step with include/gava_hip.h")
+    # the training head's structs report through their own call (gava_struct_sizes keeps its list)
+    for name in ("gava_train_criterion", "gava_train_criterion_backward"):
+        getattr(lib, name).argtypes, getattr(lib, name).restype = [C.POINTER(TrainCriterionArgs), _vp], C.c_int
+    for name in ("gava_train_head", "gava_train_head_backward"):
+        getattr(lib, name).argtypes, getattr(lib, name).restype = [C.POINTER(TrainHeadArgs), _vp], C.c_int
+    train_mirrors = [TrainCriterionArgs, TrainHeadArgs]
+    lib.gava_train_struct_sizes.argtypes, lib.gava_train_struct_sizes.restype = [C.POINTER(C.c_size_t), C.c_int], C.c_int
+    if lib.gava_train_struct_sizes(sizes, len(train_mirrors)) != len(train_mirrors):
+        raise GavaError("libgava_hip.so and gava_clip_amd/hip.py disagree on the number of training-head ABI structs")
+    for cls, sz in zip(train_mirrors, sizes):
         if C.sizeof(cls) != sz:
             raise GavaError(f"ctypes mirror {cls.__name__} is {C.sizeof(cls)} bytes, the library's struct {sz}: gava_clip_amd/hip.py is out of "
                             f"step with include/gava_hip.h")
@@ -553,3 +585,109 @@ def view_scores(logits):
     with torch.cuda.device(logits.device):
         check(load().gava_view_scores(C.byref(a), stream_ptr(logits.device)), "gava_view_scores")
     return scores, top1
+
+
+# ---- training head and criterion (gava_train_criterion*, gava_train_head*) ----------------------------------------------------
+
+def _f32(t, what):
+    assert t.is_cuda and t.dtype == torch.float32, f"{what} must be a device fp32 tensor"
+    return t
+
+
+def train_criterion(logits, labels, *, weighted=False, alpha=0.25, gamma=2.0, beta=0.0, scale=1.0, conf=None, check_labels=False):
+    """Per-sample cross-entropy (times the ordinal-focal weight when `weighted`), its mean, the argmax and the hit count
+    (gava_train_criterion; the formula is in include/gava_hip.h).  logits: device fp32 [B, C] with a contiguous class dimension
+    (any row stride); labels: device int64 [B].  conf: optional device int32 [C, C], ACCUMULATED: conf[label, top1] += 1.
+    -> dict(loss (0-dim), per_sample [B], weight [B], top1 int32 [B], hits int32 (0-dim), conf, saved [B, 4]).
+    Labels outside [0, C) are clamped by the kernel; check_labels=True refuses them here instead, at the price of a host
+    sync.  Two launches, no sync otherwise."""
+    _f32(logits, "logits")
+    assert logits.dim() == 2 and (logits.shape[1] == 1 or logits.stride(1) == 1), "logits must be [B, C] with a contiguous class dimension"
+    if labels.is_floating_point() or labels.dim() != 1:
+        raise GavaError("gava_train_criterion takes integer class labels [B]; soft (mixup) targets are not supported")
+    B, Cn = logits.shape
+    assert labels.shape[0] == B and labels.is_cuda
+    labels = labels.to(torch.int64).contiguous()
+    if check_labels and bool(((labels < 0) | (labels >= Cn)).any()):
+        raise GavaError(f"labels outside [0, {Cn})")
+    dev = logits.device
+    out = dict(loss=torch.empty((), dtype=torch.float32, device=dev), per_sample=torch.empty(B, dtype=torch.float32, device=dev),
+               weight=torch.empty(B, dtype=torch.float32, device=dev), top1=torch.empty(B, dtype=torch.int32, device=dev),
+               hits=torch.empty((), dtype=torch.int32, device=dev), conf=conf,
+               saved=torch.empty(B, 4, dtype=torch.float32, device=dev))
+    if conf is not None:
+        assert conf.is_cuda and conf.dtype == torch.int32 and tuple(conf.shape) == (Cn, Cn) and conf.is_contiguous()
+    a = TrainCriterionArgs()
+    a.logits, a.ld_logits, a.labels = ptr(logits), (logits.stride(0) if B > 1 else max(logits.stride(0), Cn)), ptr(labels)
+    a.B, a.C, a.weighted = B, Cn, int(weighted)
+    a.alpha, a.gamma, a.beta, a.scale = alpha, gamma, beta, scale
+    a.loss, a.per_sample, a.weight, a.top1, a.hits = ptr(out["loss"]), ptr(out["per_sample"]), ptr(out["weight"]), ptr(out["top1"]), ptr(out["hits"])
+    a.conf, a.saved = ptr(conf), ptr(out["saved"])
+    with torch.cuda.device(dev):
+        check(load().gava_train_criterion(C.byref(a), stream_ptr(dev)), "gava_train_criterion")
+    out["labels"] = labels
+    return out
+
+
+def train_criterion_backward(logits, labels, saved, grad_loss):
+    """dlogits [B, C] of train_criterion's loss; grad_loss: the upstream gradient, a DEVICE fp32 scalar (never read on the host)."""
+    _f32(logits, "logits"), _f32(grad_loss, "grad_loss")
+    B, Cn = logits.shape
+    assert grad_loss.numel() == 1 and labels.dtype == torch.int64 and labels.is_contiguous() and tuple(saved.shape) == (B, 4)
+    dlogits = torch.empty(B, Cn, dtype=torch.float32, device=logits.device)
+    a = TrainCriterionArgs()
+    a.logits, a.ld_logits, a.labels = ptr(logits), (logits.stride(0) if B > 1 else max(logits.stride(0), Cn)), ptr(labels)
+    a.B, a.C, a.saved, a.grad_loss, a.dlogits, a.ld_dlogits = B, Cn, ptr(saved), ptr(grad_loss), ptr(dlogits), Cn
+    with torch.cuda.device(logits.device):
+        check(load().gava_train_criterion_backward(C.byref(a), stream_ptr(logits.device)), "gava_train_criterion_backward")
+    return dlogits
+
+
+def _train_head_args(kept):
+    a = TrainHeadArgs()
+    for k in ("video", "text", "class_offsets", "logit_scale", "logit_bias", "logits", "text_features", "video_norm", "video_inv",
+              "text_norm", "text_inv", "class_mean"):
+        setattr(a, k, ptr(kept.get(k)))
+    a.B, a.C, a.P, a.E = kept["B"], kept["C"], kept["P"], kept["E"]
+    return a
+
+
+def train_head(video, text, class_offsets, logit_scale, logit_bias=None):
+    """Forward of the training head (gava_train_head): raw video [B, E] and prompt features [P, E], class_offsets int32 [C+1] on
+    the device (prompts of class c = rows offsets[c] .. offsets[c+1]; offsets[C] == P is the caller's promise - it is not read
+    here, the kernels clamp) -> dict with logits [B, C], text_features [C, E] and what train_head_backward reuses."""
+    video, text = _f32(video, "video").contiguous(), _f32(text, "text").contiguous()
+    assert class_offsets.is_cuda and class_offsets.dtype == torch.int32 and class_offsets.is_contiguous() and class_offsets.dim() == 1
+    B, E = video.shape
+    P, Cn = text.shape[0], class_offsets.numel() - 1
+    assert text.shape[1] == E and Cn >= 1
+    dev = video.device
+    new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+    kept = dict(B=B, C=Cn, P=P, E=E, class_offsets=class_offsets, logit_scale=_f32(logit_scale, "logit_scale").reshape(1),
+                logit_bias=_f32(logit_bias, "logit_bias").reshape(1) if logit_bias is not None else None,
+                logits=new(B, Cn), text_features=new(Cn, E), video_norm=new(B, E), video_inv=new(B), text_norm=new(P, E),
+                text_inv=new(P), class_mean=new(Cn, E))
+    a = _train_head_args(dict(kept, video=video, text=text))
+    with torch.cuda.device(dev):
+        check(load().gava_train_head(C.byref(a), stream_ptr(dev)), "gava_train_head")
+    return kept
+
+
+def train_head_backward(kept, dlogits, dtext_features=None):
+    """-> (dvideo [B, E], dtext [P, E], dlogit_scale [1], dlogit_bias [1] or None) from train_head's dict."""
+    dev = dlogits.device
+    new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+    B, Cn, P, E = kept["B"], kept["C"], kept["P"], kept["E"]
+    dlogits = _f32(dlogits, "dlogits").contiguous()
+    assert tuple(dlogits.shape) == (B, Cn)
+    if dtext_features is not None:
+        dtext_features = _f32(dtext_features, "dtext_features").contiguous()
+        assert tuple(dtext_features.shape) == (Cn, E)
+    dvideo, dtext, dls, ws = new(B, E), new(P, E), new(1), new((B + Cn) * E)
+    dlb = new(1) if kept["logit_bias"] is not None else None
+    a = _train_head_args(kept)                       # (the backward reads neither the raw features nor text_features)
+    a.dlogits, a.dtext_features = ptr(dlogits), ptr(dtext_features)
+    a.dvideo, a.dtext, a.dlogit_scale, a.dlogit_bias, a.workspace = ptr(dvideo), ptr(dtext), ptr(dls), ptr(dlb), ptr(ws)
+    with torch.cuda.device(dev):
+        check(load().gava_train_head_backward(C.byref(a), stream_ptr(dev)), "gava_train_head_backward")
+    return dvideo, dtext, dls, dlb

@@ -360,6 +360,9 @@ class _HipHost:
         # training: keep the backward's activations (~21 GB at B = 64, T = 8) instead of recomputing them per block, as
         # long as they fit this budget; beyond it the backward recomputes from the block inputs only
         self.keep_activation_bytes = int(float(os.environ.get("GAVA_KEEP_ACT_GB", "96")) * 2 ** 30)
+        # the similarity head under autograd: "torch" = traced torch ops (_train_head), "hip" = training.HeadFn (gava_train_head)
+        self.train_head = os.environ.get("GAVA_TRAIN_HEAD", "torch")
+        self._head_offsets = (None, None)
         self._text_stream = None
         self._text_cache = None
         self.gather_across_ranks = True     # RCCL all-gather of clip embeddings when world_size > 1
@@ -1017,6 +1020,25 @@ class VitaCLIP(nn.Module, _HipHost):
         self.last.update(video_features=vf.detach(), summary=summary.detach())
         return logits
 
+    def _train_head_hip(self, video, text, summary, desc_wise):
+        """_train_head as one autograd node over the HIP head (training.HeadFn; train_head = "hip"): the same logits,
+        text_features and `last` entries, the backward in two launches.  last["head_fn_calls"] counts its uses."""
+        from .training import HeadFn
+        assert not desc_wise
+        counts = self.prompt_learner.kv_counts if self.use_text_prompt_learning else [1] * text.shape[0]
+        key = (tuple(counts), video.device)
+        if self._head_offsets[0] != key:
+            off = [0]
+            for k in counts:
+                off.append(off[-1] + int(k))
+            self._head_offsets = (key, torch.tensor(off, dtype=torch.int32).to(video.device))
+        if text.shape[0] != sum(counts):
+            raise hip.GavaError(f"{text.shape[0]} prompt features for {sum(counts)} prompts")
+        logits, self.text_features = HeadFn.apply(video, text, self.logit_scale, self.logit_bias, self._head_offsets[1])
+        self.last.update(video_features=logits.grad_fn.saved_tensors[HeadFn.SAVED.index("video_norm")], summary=summary.detach(),
+                         head_fn_calls=self.last.get("head_fn_calls", 0) + 1)
+        return logits
+
     # ---- forward ------------------------------------------------------------------------------
     def forward(self, x: torch.Tensor, memory=None, video_nte=None, desc_wise=False):
         if not x.is_cuda:
@@ -1188,7 +1210,12 @@ class VitaCLIP(nn.Module, _HipHost):
             text.record_stream(torch.cuda.current_stream(x.device))
         if torch.is_grad_enabled() and (text.requires_grad or video.requires_grad or self.logit_scale.requires_grad):
             # training: the 2*B*C*E-flop head is traced by torch so that d logits reaches both towers' HIP backward
-            logits = self._train_head(video, text, summary, desc_wise)
+            if self.train_head == "hip":
+                logits = self._train_head_hip(video, text, summary, desc_wise)
+            elif self.train_head == "torch":
+                logits = self._train_head(video, text, summary, desc_wise)
+            else:
+                raise hip.GavaError(f"train_head must be 'torch' or 'hip', got {self.train_head!r}")
         else:
             Bg, Cn = video.shape[0], text.shape[0]
             n_kv = self.prompt_learner.n_kv if self.use_text_prompt_learning else 1

@@ -439,3 +439,89 @@ class VisionTowerFn(torch.autograd.Function):
             gi = g.get(name)
             out.append(gi.reshape(p.shape).to(p.dtype) if (gi is not None and p.requires_grad) else None)
         return (None, None, None, *out)
+
+
+# =================================================================================================
+# The step's tail: similarity head and criterion on the device (opt-in)
+# =================================================================================================
+# With VitaCLIP.train_head = "hip" the head between the towers' outputs and the logits is HeadFn (the inference head's kernels
+# forward, fp32 MFMA tiles backward) instead of the traced torch ops of VitaCLIP._train_head, and TrainCriterion is the
+# criterion of training/train.py:360-362,446-452 (cross-entropy x ordinal-focal weight of training/loss_utils.py:9-46, mean)
+# as two launches forward and one backward.  Not covered: soft (mixup) labels, the sigmoid memory criterion and the InfoNCE
+# variants of loss_utils.py - those stay torch code on the caller's side.
+
+class HeadFn(torch.autograd.Function):
+    """(logits [B, C], text_features [C, E]) = head(video [B, E], text [P, E], logit_scale, logit_bias or None, class_offsets):
+    gava_train_head / gava_train_head_backward.  Saved for the backward (save_for_backward, so they die with the graph and an
+    in-place edit of the logits is caught): the unit rows, their inverse norms, the class means and the logits - (B + P + 2C) x E
+    floats, none of the towers' activations.  text_features carries a gradient back (the support-memory head reads it); an
+    unused output costs nothing (its gradient stays undefined -> NULL)."""
+    SAVED = ("video_norm", "video_inv", "text_norm", "text_inv", "class_mean", "logits", "class_offsets", "logit_scale", "logit_bias")
+
+    @staticmethod
+    def forward(fctx, video, text, logit_scale, logit_bias, offsets):
+        kept = hip.train_head(video.detach().float(), text.detach().float(), offsets, logit_scale.detach().float(),
+                              logit_bias.detach().float() if logit_bias is not None else None)
+        fctx.save_for_backward(*[kept[k] for k in HeadFn.SAVED])
+        fctx.dims = {k: kept[k] for k in ("B", "C", "P", "E")}
+        fctx.set_materialize_grads(False)
+        fctx.shapes = (logit_scale.shape, logit_bias.shape if logit_bias is not None else None)
+        fctx.dtypes = (video.dtype, text.dtype, logit_scale.dtype)
+        return kept["logits"], kept["text_features"]
+
+    @staticmethod
+    def backward(fctx, dlogits, dtf):
+        kept = dict(zip(HeadFn.SAVED, fctx.saved_tensors), **fctx.dims)
+        if dlogits is None:
+            dlogits = torch.zeros_like(kept["logits"])
+        dvideo, dtext, dls, dlb = hip.train_head_backward(kept, dlogits.float(), dtf.float() if dtf is not None else None)
+        ls_shape, lb_shape = fctx.shapes
+        return (dvideo.to(fctx.dtypes[0]), dtext.to(fctx.dtypes[1]), dls.reshape(ls_shape).to(fctx.dtypes[2]),
+                dlb.reshape(lb_shape) if dlb is not None else None, None)
+
+
+class _CriterionFn(torch.autograd.Function):
+    @staticmethod
+    def forward(fctx, logits, labels, crit):
+        out = hip.train_criterion(logits.detach(), labels, weighted=crit.focal_ordinal, alpha=crit.alpha, gamma=crit.gamma,
+                                  beta=crit.beta, scale=crit.scale, conf=crit.conf, check_labels=crit.check_labels)
+        fctx.save_for_backward(logits.detach(), out["labels"], out["saved"])
+        crit.last = {k: out[k] for k in ("per_sample", "weight", "top1", "hits", "conf")}
+        return out["loss"]
+
+    @staticmethod
+    def backward(fctx, g):
+        logits, labels, saved = fctx.saved_tensors
+        return hip.train_criterion_backward(logits, labels, saved, g.float().contiguous()), None, None
+
+
+class TrainCriterion:
+    """loss = crit(logits, labels): the criterion of the reference's training loop on the device (gava_train_criterion).
+    focal_ordinal=False is torch.nn.CrossEntropyLoss()(logits, labels); True multiplies every sample's cross-entropy by
+    scale * (beta * |label - argmax| / (C - 1) + alpha * (1 - p_label)^gamma) before the mean (training/train.py:361-362 uses
+    gamma 2, alpha 0.25 and beta 0.2 for UPDRS).  Any device fp32 [B, C] logits with int64 (integer) labels [B]; soft targets
+    are refused.  After a call, `last` holds device tensors per_sample, weight, top1 (int32), hits (int32 scalar) and conf:
+    nothing is read back - read hits when you print.  conf: pass track_confusion=True to keep an int32 [C, C] matrix
+    conf[label, top1] that every call adds to (reset_confusion() clears it).  check_labels=True validates the label range on
+    the host (a sync); by default out-of-range labels are clamped on the device."""
+
+    def __init__(self, focal_ordinal=False, alpha=0.25, gamma=2.0, beta=0.0, scale=1.0, track_confusion=False, check_labels=False):
+        if focal_ordinal and not gamma >= 1.0:
+            raise hip.GavaError("TrainCriterion needs gamma >= 1: the focal factor's derivative is unbounded at p = 1 below that")
+        self.focal_ordinal, self.alpha, self.gamma, self.beta, self.scale = bool(focal_ordinal), float(alpha), float(gamma), float(beta), float(scale)
+        self.track_confusion, self.check_labels = track_confusion, check_labels
+        self.conf, self.last = None, {}
+
+    def reset_confusion(self):
+        self.conf = None
+
+    def __call__(self, logits, labels):
+        if not (torch.is_tensor(labels) and not labels.is_floating_point() and labels.dim() == 1):
+            raise hip.GavaError("TrainCriterion takes integer class labels [B]; soft (mixup) targets are not supported")
+        if not (logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2):
+            raise hip.GavaError("TrainCriterion takes device fp32 logits [B, C]")
+        if logits.shape[1] > 1 and logits.stride(1) != 1:
+            logits = logits.contiguous()
+        if self.track_confusion and (self.conf is None or self.conf.shape[0] != logits.shape[1] or self.conf.device != logits.device):
+            self.conf = torch.zeros(logits.shape[1], logits.shape[1], dtype=torch.int32, device=logits.device)
+        return _CriterionFn.apply(logits, labels.to(logits.device), self)

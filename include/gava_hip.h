@@ -556,6 +556,69 @@ int gava_patchify(const gava_patchify_args* a, gava_stream_t stream);
 /* fp32 -> h16 conversion of a contiguous array (weight packing at load time). */
 int gava_convert_h16(const float* in, void* out, size_t n, int prec, gava_stream_t stream);
 
+/* ---- training head and criterion (opt-in: VitaCLIP.train_head = "hip", gava_clip_amd.TrainCriterion) ----------------------
+ *
+ * Criterion of the reference's training loop (training/train.py:360-362,446-452, training/loss_utils.py:9-46): per-sample
+ * cross-entropy, optionally times the ordinal-focal weight, then the mean.  Per sample i with label y (clamped to [0, C) on
+ * the device), all in fp32:
+ *   p = softmax(z_i);  ce_i = logsumexp(z_i) - z_iy;  k_i = argmax_c z_ic (the lowest index on ties)
+ *   w_i = scale * (beta * |y - k_i| / (C - 1) + alpha * (1 - p_y)^gamma);   l_i = weighted ? ce_i * w_i : ce_i
+ *   loss = mean_i l_i;  hits = #{i : k_i == y};  conf[y][k_i] += 1 (optional, int32 [C][C], ACCUMULATED by integer atomics)
+ * The forward leaves four floats per sample in `saved` (row max, log of the sum of exp, the gradient's factor a_i, 1 - p_y);
+ * the backward reads them, the logits, the labels and the upstream gradient of `loss` FROM DEVICE MEMORY (grad_loss, one
+ * float: GradScaler's scale never visits the host) and writes
+ *   dlogits[i][c] = a_i * (p_c - [c == y]) * grad_loss / B,   a_i = w_i + ce_i * scale * alpha * gamma * (1 - p_y)^(gamma-1) * p_y
+ * (a_i = 1 unweighted; the ordinal term has no gradient, as in the reference, whose autograd passes the focal factor only).
+ * GAVA_EINVAL: weighted with gamma < 1 (the derivative is unbounded at p_y = 1) or C < 2, B < 1, C < 1, a null pointer among
+ * the required ones (forward: logits, labels, loss, per_sample, weight, top1, hits, saved; backward: logits, labels, saved,
+ * grad_loss, dlogits).  No floating-point atomics: the same bits on every run.  Two launches forward, one backward, no
+ * host synchronisation. */
+typedef struct {
+  const float* logits; int64_t ld_logits;     /* fp32 [B][C], rows ld_logits elements apart */
+  const int64_t* labels;                      /* [B] */
+  int B, C, weighted;
+  float alpha, gamma, beta, scale;
+  float* loss; float* per_sample; float* weight; int32_t* top1; int32_t* hits;
+  int32_t* conf;                              /* optional */
+  float* saved;                               /* [B][4] */
+  const float* grad_loss; float* dlogits; int64_t ld_dlogits;     /* backward only */
+} gava_train_criterion_args;
+int gava_train_criterion(const gava_train_criterion_args* a, gava_stream_t stream);
+int gava_train_criterion_backward(const gava_train_criterion_args* a, gava_stream_t stream);
+
+/* The similarity head under autograd (VitaCLIP_model.py:248,255,287-293,308-309), fp32.  video [B][E] and text [P][E] are
+ * the towers' raw outputs; class_offsets int32 [C+1] (device) gives the prompts of class c as rows offsets[c] .. offsets[c+1]
+ * of text, offsets[C] == P (one prompt per class, n_kv per class, or the ragged descriptor mode).
+ *   logits[b][c] = exp(logit_scale) * <vn_b, m_c> + logit_bias,  vn = video / |video|,  m_c = mean of the unit prompt rows of c
+ *   text_features[c] = m_c / |m_c|
+ * The forward runs the kernels of gava_similarity_head: with equal counts, logits and text_features have that head's bits.
+ * It keeps video_norm [B][E], video_inv [B], text_norm [P][E], text_inv [P] (unit rows and 1 / |row|) and class_mean [C][E].
+ * A class without prompts (offsets[c] == offsets[c+1]) has the class mean 0: its logits are logit_bias, its text_features row
+ * is undefined (0 / 0), and no prompt row receives its gradient.
+ * The backward takes dlogits [B][C] (contiguous) and optionally dtext_features [C][E] (NULL = zero) plus what the forward
+ * kept and its logits - it reads neither video, text nor text_features, which may be NULL there - and writes dvideo [B][E], dtext [P][E], dlogit_scale (1), dlogit_bias (1, optional):
+ *   dvn = s * dlogits @ m,  dm = s * dlogits^T @ vn + (dtf - tf <tf, dtf>) / |m|,  s = exp(logit_scale)   (fp32 MFMA tiles,
+ *   zero-filled past B, C, E)
+ *   dlogit_scale = sum dlogits * (logits - logit_bias),  dlogit_bias = sum dlogits              (one wave, fixed order)
+ *   dvideo = (dvn - vn <vn, dvn>) / |video|;  per prompt k of class c: dtn = dm_c / count_c, dtext = (dtn - tn <tn, dtn>) / |text_k|
+ * workspace: (B + C) * E floats.  E % 4 == 0.  Two launches; no atomics, the same bits on every run. */
+typedef struct {
+  const float* video; const float* text; const int32_t* class_offsets;
+  const float* logit_scale; const float* logit_bias;        /* logit_bias optional */
+  int B, C, P, E;
+  float* logits; float* text_features;
+  float* video_norm; float* video_inv; float* text_norm; float* text_inv; float* class_mean;
+  const float* dlogits; const float* dtext_features;        /* backward only from here; dtext_features optional */
+  float* dvideo; float* dtext; float* dlogit_scale; float* dlogit_bias;
+  float* workspace;
+} gava_train_head_args;
+int gava_train_head(const gava_train_head_args* a, gava_stream_t stream);
+int gava_train_head_backward(const gava_train_head_args* a, gava_stream_t stream);
+
+/* sizeof of the two structs above, in that order, like gava_struct_sizes (whose list is closed at its 17 entries: a binding
+ * compares that call's return value with its own count).  Writes min(cap, 2) entries, returns 2. */
+int gava_train_struct_sizes(size_t* out, int cap);
+
 /* sizeof of every ABI struct as the library was compiled, in the order gemm_args, layernorm_args, attention_args,
  * attention_f32_args, clip_desc, vision_layer, vision_layer8, vision_model, text_layer, text_model, layernorm_bwd_args,
  * attention_bwd_args, vision_saved, preprocess_args, patchify_args, preprocess_clips_args, view_scores_args.  Writes
