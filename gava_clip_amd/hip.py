@@ -415,9 +415,12 @@ def pack_w8(w, prec):
     return hi, w8.to(w.device), e, s8.to(w.device).contiguous()
 
 
-def convert_h16(x, prec):
+def convert_h16(x, prec, out=None):
+    """fp32 -> 16-bit copy in `prec`; into `out` (contiguous, same number of elements) when given."""
     x = x.contiguous()
-    out = torch.empty(x.shape, dtype=h16_dtype(prec), device=x.device)
+    if out is None:
+        out = torch.empty(x.shape, dtype=h16_dtype(prec), device=x.device)
+    assert out.is_contiguous() and out.numel() == x.numel() and out.dtype == h16_dtype(prec)
     check(load().gava_convert_h16(ptr(x), ptr(out), x.numel(), prec, stream_ptr()), "gava_convert_h16")
     return out
 

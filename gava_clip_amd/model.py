@@ -371,6 +371,7 @@ class _HipHost:
         self._shape = dict(shape)
         self._packed = None
         self._packed_key = None
+        self._bwd_packs = {}
         self._ws = {}
         self.last = {}
 
@@ -441,20 +442,16 @@ class _HipHost:
                     packed["b_sqkv_wlo"][i].copy_(torch.cat([s_.q_proj.bias, s_.k_proj.bias, s_.v_proj.bias], 0).detach().float())
         packed["summary_ver"] = cur
 
-    def _pack_vision_backward(self):
+    def _backward_pack(self, tower):
+        """The training backward's bf16 weight copies of `tower` ("text" | "vision"; training.pack_*_backward), remade when
+        the pack key changes.  The vision side's trainable copies are brought up to date on every use."""
         from . import training
         key = self._pack_key()
-        if getattr(self, "_bwd_pack_v", None) is None or self._bwd_pack_v[0] != key:
-            self._bwd_pack_v = (key, training.pack_vision_backward(self))
-        training.refresh_vision_backward(self, self._bwd_pack_v[1])
-        return self._bwd_pack_v[1]
-
-    def _pack_text_backward(self):
-        from . import training
-        key = self._pack_key()
-        if getattr(self, "_bwd_pack", None) is None or self._bwd_pack[0] != key:
-            self._bwd_pack = (key, training.pack_text_backward(self))
-        return self._bwd_pack[1]
+        if self._bwd_packs.get(tower, (None,))[0] != key:
+            self._bwd_packs[tower] = (key, getattr(training, f"pack_{tower}_backward")(self))
+        if tower == "vision":
+            training.refresh_vision_backward(self, self._bwd_packs[tower][1])
+        return self._bwd_packs[tower][1]
 
     def _h16(self, t):
         return hip.convert_h16(t.detach().float(), self.prec)
@@ -997,8 +994,9 @@ class VitaCLIP(nn.Module, _HipHost):
         return A
 
     def _vision_trainables(self):
-        from .training import _vision_trainables
-        return _vision_trainables(self)
+        """Ordered (name, parameter) list of the vision-side parameters the reference leaves trainable."""
+        return [(n, p) for n, p in self.visual.named_parameters()
+                if ("summary" in n or "local" in n or "global" in n or "time_embed" in n)]
 
     def _train_head(self, video, text, summary, desc_wise):
         """Similarity head under autograd (VitaCLIP_model.py:248,255,287-293,308-309): 2*B*C*E flop on (B,E)/(C,E)

@@ -1,21 +1,33 @@
-"""Backward of the trainable subset through the HIP kernels (first stage: the text side).
+"""`loss.backward()` of the trainable subset through the HIP kernels.
 
 The reference trains `prompt_learner.ctx` (CoOp context vectors), the vision prompts and `logit_scale` with every
 transformer weight frozen (VitaCLIP_model.py:230-239; training/train.py:441-490 calls `loss.backward()`).  The
-gradient therefore only has to flow THROUGH the frozen GEMMs:
-
-    d logits -> d text features -> text_projection^T -> ln_final' (EOT rows) -> 12 x residual block' -> d ctx
-
-This module implements that chain for the text tower as a `torch.autograd.Function` around the C ABI:
-forward = `gava_text_forward_train` (keeps the fp32 input of every block), backward = per block, in reverse:
-recompute the block's activations from its saved input (LayerNorm, QKV GEMM, attention, out-proj GEMM, LayerNorm,
-fc GEMM - the forward kernels), then dgrad GEMMs on transposed weight copies + `gava_qgelu_backward`,
-`gava_layernorm_backward`, `gava_attention_backward`.  Gradient operands are bf16 (fp32 exponent range, so no
+gradient therefore only has to flow THROUGH the frozen GEMMs.  Gradient operands are bf16 (fp32 exponent range, so no
 loss scaling inside the library; the reference's fp16 autocast needs its GradScaler), accumulation fp32.
 
-The second half of this module does the same for the vision tower (prompt parameters, summary path, time_embed).
+Both towers are stacks of one residual block and share its two stages and the layout of its packed weights:
+    _block_weights     bf16 copies of the frozen weights in both orientations (forward for the recompute, transposed for dgrad)
+    _block_recompute   a block's activations from its saved fp32 input: the six forward launches
+    _block_backward    MLP' and attention' (dgrad GEMMs, fused QuickGELU', LayerNorm', gava_attention_backward); LN1' is the caller's
+Text (`TextTowerFn`; `gava_text_forward_train` keeps the fp32 input of every block), `text_backward`:
+    d text features -> text_projection^T -> ln_final' (EOT rows) -> 12 x (recompute, backward, LN1') -> d ctx
+Vision (`VisionTowerFn`; the forward keeps the blocks' activations or, above `keep_activation_bytes`, their fp32 inputs).
+Trainable (VitaCLIP_model.py:230-234: names containing summary / local / global / time_embed): visual.global_prompts
+(layers,G,D), visual.time_embed (T,D) and per block local_prompts (1,T,D), summary_ln.{weight,bias},
+summary_attn_layer.{q,k,v,out}_proj.{weight,bias}.  `vision_backward` runs VitaCLIP_vision_encoder.py:102-132 and
+VitaCLIP_vision_encoder_utils.py:155-203 in reverse as a list of stages, on scratch that lives for the one call:
+    _head_backward       mean over T, proj^T, ln_post' on the CLS rows
+    per block: _prompt_recompute   cls_proj, summary_ln, summary attention, the prompt rows SIDE every frame attends to
+               _main_activations   SIDE's K/V and the main rows' qkv / X1 / pre: what the forward kept, or _block_recompute
+               _block_backward     on all B*T*197 rows, or _cls_only_backward for a kept last block
+               _prompt_backward    d SIDE -> d global / local prompts and, through the summary path, the gradients of
+                                   summary_ln / summary_attn_layer (wgrad = gava_gemm on transposed operands) and the CLS rows' share
+               LN1' of the main rows
+    _embedding_backward  ln_pre', sum over tokens = d time_embed
+The second half of the module is the step's tail: similarity head and criterion on the device.
 """
 import ctypes as C
+from types import SimpleNamespace
 
 import torch
 
@@ -24,25 +36,88 @@ from . import hip
 BWD = hip.PREC_BF16
 
 
-def _bf16(t):
-    return hip.convert_h16(t.detach().float().contiguous(), BWD)
+def f32(p):
+    return p.detach().float().contiguous()
 
+
+def new(dev, *shape, dtype=torch.bfloat16):
+    return torch.empty(*shape, dtype=dtype, device=dev)
+
+
+def split3(t):
+    """[rows][3W] -> its q, k, v column blocks."""
+    W = t.shape[1] // 3
+    return t[:, :W], t[:, W:2 * W], t[:, 2 * W:]
+
+
+def _bf16(t):
+    return hip.convert_h16(f32(t), BWD)
+
+
+def _both(w):
+    """Weight [out][in] -> (bf16 copy for the recompute, bf16 copy of its transpose for dgrad)."""
+    return _bf16(w), _bf16(w.detach().t())
+
+
+def _block_weights(w_qkv, b_qkv, out_proj, fc1, fc2):
+    """The pack entries every transformer block has, under the same names in both towers."""
+    P = dict(b_qkv=f32(b_qkv), b_out=f32(out_proj.bias), b_fc1=f32(fc1.bias), w_fc2_t=_bf16(fc2.weight.detach().t()))
+    P["w_qkv"], P["w_qkv_t"] = _both(w_qkv)
+    P["w_out"], P["w_out_t"] = _both(out_proj.weight)
+    P["w_fc1"], P["w_fc1_t"] = _both(fc1.weight)
+    return P
+
+
+def _block_scratch(dev, R, W, F, recompute=False):
+    """Scratch of the block stages for R rows of width W, allocated once per backward call."""
+    s = SimpleNamespace(dx16=new(dev, R, W), dhid=new(dev, R, F), dmix=new(dev, R, W), dqkv=new(dev, R, 3 * W),
+                        dxn=new(dev, R, W, dtype=torch.float32))
+    if recompute:
+        s.xn, s.qkv, s.mix, s.pre, s.X1 = new(dev, R, W), new(dev, R, 3 * W), new(dev, R, W), new(dev, R, F), new(dev, R, W, dtype=torch.float32)
+    return s
+
+
+def _block_recompute(P, ln, X0, s, **attn):
+    """Recompute a block from its fp32 input X0 with the forward kernels (bf16 operands): fills s.qkv, s.X1 (the stream
+    after the attention branch) and s.pre (the fc1 pre-activation).  ln = (ln1 weight, ln1 bias, ln2 weight, ln2 bias);
+    `attn` are the tower's keyword arguments of hip.attention."""
+    W = X0.shape[1]
+    hip.layernorm(X0, ln[0], ln[1], out16=s.xn, prec=BWD)
+    hip.gemm(s.xn, P["w_qkv"], P["b_qkv"], s.qkv, epilogue=hip.EPI_H16, prec=BWD, scale_cols=W, scale=0.125)
+    hip.attention(*split3(s.qkv), s.mix, prec=BWD, **attn)
+    hip.gemm(s.mix, P["w_out"], P["b_out"], s.X1, epilogue=hip.EPI_F32, prec=BWD, resid=X0)
+    hip.layernorm(s.X1, ln[2], ln[3], out16=s.xn, prec=BWD)
+    hip.gemm(s.xn, P["w_fc1"], P["b_fc1"], s.pre, epilogue=hip.EPI_H16, prec=BWD)
+
+
+def _mlp_backward(P, ln2_g, dX, s, X1, pre, act):
+    """MLP branch x2 = x1 + fc2(gelu(fc1(ln_2 x1))) (VitaCLIP_text_encoder.py:73-77,86; vision_encoder_utils.py:109-115,199):
+    dX (fp32; s.dx16 = its bf16 copy, written by the LayerNorm' that produced it) takes the branch's share, then out_proj^T
+    -> s.dmix.  `act`: storage type of the kept activations (None: the gradients' bf16)."""
+    hip.gemm(s.dx16, P["w_fc2_t"], None, s.dhid, epilogue=hip.EPI_H16_QGELU_BWD, prec=BWD, aux=pre, aux_prec=act)   # fc2^T, gelu' fused
+    hip.gemm(s.dhid, P["w_fc1_t"], None, s.dxn, epilogue=hip.EPI_F32, prec=BWD)
+    hip.layernorm_backward(X1, ln2_g, s.dxn, dX, accumulate=True, dx16=s.dx16)
+    hip.gemm(s.dx16, P["w_out_t"], None, s.dmix, epilogue=hip.EPI_H16, prec=BWD)
+
+
+def _block_backward(P, ln2_g, dX, s, X1, pre, qkv, act, **attn):
+    """MLP' and attention' of a block on all its rows; s.dxn is left holding the input of LN1' for the caller.  Attention
+    branch: x1 = x0 + out_proj(attn(in_proj(ln_1 x0))) (VitaCLIP_text_encoder.py:81-85; vision_encoder_utils.py:61-81,190-191);
+    `attn` are the tower's keyword arguments of hip.attention_backward."""
+    _mlp_backward(P, ln2_g, dX, s, X1, pre, act)
+    hip.attention_backward(*split3(qkv), s.dmix, *split3(s.dqkv), prec=BWD, q_scale=0.125, act_prec=act, **attn)
+    hip.gemm(s.dqkv, P["w_qkv_t"], None, s.dxn, epilogue=hip.EPI_F32, prec=BWD)
+
+
+# ---- text tower: gradient of the context vectors ------------------------------------------------
 
 def pack_text_backward(model):
     """bf16 copies of the frozen text weights in both orientations (forward for the recompute, transposed for dgrad)."""
     t = model.textual
-    layers = []
-    for blk in t.transformer.resblocks:
-        f32 = lambda p: p.detach().float().contiguous()
-        layers.append(dict(
-            w_qkv=_bf16(blk.attn.in_proj_weight), w_qkv_t=_bf16(blk.attn.in_proj_weight.detach().t()),
-            b_qkv=f32(blk.attn.in_proj_bias),
-            w_out=_bf16(blk.attn.out_proj.weight), w_out_t=_bf16(blk.attn.out_proj.weight.detach().t()),
-            b_out=f32(blk.attn.out_proj.bias),
-            w_fc=_bf16(blk.mlp.c_fc.weight), w_fc_t=_bf16(blk.mlp.c_fc.weight.detach().t()), b_fc=f32(blk.mlp.c_fc.bias),
-            w_proj_t=_bf16(blk.mlp.c_proj.weight.detach().t()),
-            ln1_g=f32(blk.ln_1.weight), ln1_b=f32(blk.ln_1.bias), ln2_g=f32(blk.ln_2.weight), ln2_b=f32(blk.ln_2.bias)))
-    return dict(layers=layers, lnf_g=t.ln_final.weight.detach().float().contiguous(),
+    layers = [dict(_block_weights(blk.attn.in_proj_weight, blk.attn.in_proj_bias, blk.attn.out_proj, blk.mlp.c_fc, blk.mlp.c_proj),
+                   ln=(f32(blk.ln_1.weight), f32(blk.ln_1.bias), f32(blk.ln_2.weight), f32(blk.ln_2.bias)))
+              for blk in t.transformer.resblocks]
+    return dict(layers=layers, lnf_g=f32(t.ln_final.weight),
                 # out = x @ text_projection (W,E): dx = dout @ text_projection^T = gemm(A = dout, W = text_projection)
                 w_tproj=_bf16(t.text_projection))
 
@@ -76,44 +151,21 @@ def text_forward_train(model, ctx_param):
 def text_backward(model, saved, dtext):
     """d(text features) (C,E) -> d ctx (C, n_ctx, W), through the frozen text tower."""
     sh = model._shape
-    pk = model._pack()
-    bw = model._pack_text_backward()
-    n, L, W, H, E, n_ctx = pk["tokens"].shape[0], model.text_rows_per_prompt, sh["W"], sh["TH"], sh["E"], sh["n_ctx"]
-    R = n * L
-    dev = dtext.device
-    bf = torch.bfloat16
-    new = lambda *s, dtype=bf: torch.empty(*s, dtype=dtype, device=dev)
-    eot = pk["eot"]
+    pk, bw = model._pack(), model._backward_pack("text")
+    n, L, W, H, n_ctx = pk["tokens"].shape[0], model.text_rows_per_prompt, sh["W"], sh["TH"], sh["n_ctx"]
+    R, dev, eot = n * L, dtext.device, pk["eot"]
     dX = torch.zeros(R, W, dtype=torch.float32, device=dev)
     # text_projection^T and ln_final' on the EOT rows (VitaCLIP_text_encoder.py:164-170)
-    dtext16 = hip.convert_h16(dtext.float().contiguous(), BWD)
-    dEOT = new(n, W, dtype=torch.float32)
-    hip.gemm(dtext16, bw["w_tproj"], None, dEOT, epilogue=hip.EPI_F32, prec=BWD)
+    dEOT = new(dev, n, W, dtype=torch.float32)
+    hip.gemm(hip.convert_h16(dtext.float(), BWD), bw["w_tproj"], None, dEOT, epilogue=hip.EPI_F32, prec=BWD)
     hip.layernorm_backward(saved[sh["TL"]], bw["lnf_g"], dEOT, dX, x_row_index=eot, dx_row_index=eot, rows=n)
-    xn, qkv, mix, pre = new(R, W), new(R, 3 * W), new(R, W), new(R, 4 * W)
-    X1, dx16, dhid, dmix, dqkv = new(R, W, dtype=torch.float32), new(R, W), new(R, 4 * W), new(R, W), new(R, 3 * W)
-    dxn = new(R, W, dtype=torch.float32)
-    hip.check(hip.load().gava_convert_h16(hip.ptr(dX), hip.ptr(dx16), dX.numel(), BWD, hip.stream_ptr()), "convert")
+    s = _block_scratch(dev, R, W, 4 * W, recompute=True)
+    hip.convert_h16(dX, BWD, out=s.dx16)
     for i in reversed(range(sh["TL"])):
         P, X0 = bw["layers"][i], saved[i]
-        # ---- recompute the block from its input (forward kernels, bf16 operands)
-        hip.layernorm(X0, P["ln1_g"], P["ln1_b"], out16=xn, prec=BWD)
-        hip.gemm(xn, P["w_qkv"], P["b_qkv"], qkv, epilogue=hip.EPI_H16, prec=BWD, scale_cols=W, scale=0.125)
-        hip.attention(qkv[:, :W], qkv[:, W:2 * W], qkv[:, 2 * W:], mix, batch=n, heads=H, n_q=L, n_kmain=L, prec=BWD, causal=True)
-        hip.gemm(mix, P["w_out"], P["b_out"], X1, epilogue=hip.EPI_F32, prec=BWD, resid=X0)
-        hip.layernorm(X1, P["ln2_g"], P["ln2_b"], out16=xn, prec=BWD)
-        hip.gemm(xn, P["w_fc"], P["b_fc"], pre, epilogue=hip.EPI_H16, prec=BWD)
-        # ---- MLP branch: x2 = x1 + c_proj(gelu(c_fc(ln_2 x1)))            (VitaCLIP_text_encoder.py:73-77,86)
-        #      (dx16 = bf16 copy of dX, written by the LayerNorm' that produced dX)
-        hip.gemm(dx16, P["w_proj_t"], None, dhid, epilogue=hip.EPI_H16_QGELU_BWD, prec=BWD, aux=pre)   # c_proj^T, gelu' fused
-        hip.gemm(dhid, P["w_fc_t"], None, dxn, epilogue=hip.EPI_F32, prec=BWD)
-        hip.layernorm_backward(X1, P["ln2_g"], dxn, dX, accumulate=True, dx16=dx16)
-        # ---- attention branch: x1 = x0 + out_proj(attn(in_proj(ln_1 x0)))     (VitaCLIP_text_encoder.py:81-85)
-        hip.gemm(dx16, P["w_out_t"], None, dmix, epilogue=hip.EPI_H16, prec=BWD)
-        hip.attention_backward(qkv[:, :W], qkv[:, W:2 * W], qkv[:, 2 * W:], dmix, dqkv[:, :W], dqkv[:, W:2 * W], dqkv[:, 2 * W:],
-                               batch=n, heads=H, n=L, prec=BWD, causal=True, q_scale=0.125)
-        hip.gemm(dqkv, P["w_qkv_t"], None, dxn, epilogue=hip.EPI_F32, prec=BWD)
-        hip.layernorm_backward(X0, P["ln1_g"], dxn, dX, accumulate=True, dx16=dx16)
+        _block_recompute(P, P["ln"], X0, s, batch=n, heads=H, n_q=L, n_kmain=L, causal=True)
+        _block_backward(P, P["ln"][2], dX, s, s.X1, s.pre, s.qkv, None, batch=n, heads=H, n=L, causal=True)
+        hip.layernorm_backward(X0, P["ln"][0], s.dxn, dX, accumulate=True, dx16=s.dx16)
     # x0 = [SOS | ctx[c] | suffix] + positional_embedding  (VitaCLIP_text_encoder.py:323-332,157): ctx rows 1..n_ctx
     return dX.view(n, L, W)[:, 1:1 + n_ctx].clone()
 
@@ -135,62 +187,39 @@ class TextTowerFn(torch.autograd.Function):
         return None, dctx.to(dtext.dtype)
 
 
-# =================================================================================================
-# Vision tower (second stage): gradients of the Vita-CLIP prompt parameters through the frozen ViT
-# =================================================================================================
-# Trainable on the vision side (VitaCLIP_model.py:230-234: names containing summary / local / global / time_embed):
-#   visual.global_prompts (layers,G,D), blocks.i.local_prompts (1,T,D), blocks.i.summary_ln.{weight,bias},
-#   blocks.i.summary_attn_layer.{q,k,v,out}_proj.{weight,bias}, visual.time_embed (T,D).
-# Chain (VitaCLIP_vision_encoder.py:102-132, VitaCLIP_vision_encoder_utils.py:155-203), in reverse:
-#   d cls_x -> mean over T -> proj^T -> ln_post' (CLS rows) -> 12 x block' -> ln_pre' -> sum over tokens = d time_embed
-#   block': MLP' and attention' on all B*T*197 rows (dgrad GEMMs + qgelu' + LayerNorm' + gava_attention_backward);
-#   the attention' also yields the gradient of the shared prompt K/V rows -> K/V projection^T -> norm1' ->
-#   d global_prompts, d local_prompts, and through the summary path (T-token attention, summary_ln, cls_proj) both the
-#   parameter gradients of summary_ln / summary_attn_layer (wgrad = gava_gemm on transposed operands) and a
-#   contribution to the CLS rows of dX.
-# Activations are recomputed per block from its saved fp32 input (the forward kernels, bf16 operands).
+# ---- vision tower: gradients of the Vita-CLIP prompt parameters through the frozen ViT -----------
 
-def _vision_trainables(model):
-    """Ordered (name, parameter) list of the vision-side parameters the reference leaves trainable."""
-    return [(n, p) for n, p in model.visual.named_parameters()
-            if ("summary" in n or "local" in n or "global" in n or "time_embed" in n)]
+def _summary_weights(blk):
+    """Pack entries of the summary attention's projections: the only trainable weights with bf16 copies."""
+    s, P = blk.summary_attn_layer, {}
+    P["w_sqkv"], P["w_sqkv_t"] = _both(torch.cat([s.q_proj.weight, s.k_proj.weight, s.v_proj.weight], 0))
+    P["w_sout"], P["w_sout_t"] = _both(s.out_proj.weight)
+    return P
 
 
 def pack_vision_backward(model):
+    """bf16 copies, in both orientations, of the vision block weights and of the summary path's projections."""
     v = model.visual
-    f32 = lambda p: p.detach().float().contiguous()
     layers = []
     for blk in v.blocks:
-        a, s = blk.attn, blk.summary_attn_layer
+        a = blk.attn
         wqkv = torch.cat([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight], 0).detach()
-        wsqkv = torch.cat([s.q_proj.weight, s.k_proj.weight, s.v_proj.weight], 0).detach()
         D = wqkv.shape[1]
-        layers.append(dict(
-            w_qkv=_bf16(wqkv), w_qkv_t=_bf16(wqkv.t()), b_qkv=f32(torch.cat([a.q_proj.bias, a.k_proj.bias, a.v_proj.bias], 0)),
-            w_kv=_bf16(wqkv[D:]), w_kv_t=_bf16(wqkv[D:].t()),
-            w_out=_bf16(a.out_proj.weight), w_out_t=_bf16(a.out_proj.weight.detach().t()), b_out=f32(a.out_proj.bias),
-            w_fc1=_bf16(blk.mlp.fc1.weight), w_fc1_t=_bf16(blk.mlp.fc1.weight.detach().t()), b_fc1=f32(blk.mlp.fc1.bias),
-            w_fc2_t=_bf16(blk.mlp.fc2.weight.detach().t()),
-            w_cls=_bf16(blk.cls_proj.weight), w_cls_t=_bf16(blk.cls_proj.weight.detach().t()), b_cls=f32(blk.cls_proj.bias),
-            w_sqkv=_bf16(wsqkv), w_sqkv_t=_bf16(wsqkv.t()),
-            w_sout=_bf16(s.out_proj.weight), w_sout_t=_bf16(s.out_proj.weight.detach().t())))
+        P = _block_weights(wqkv, torch.cat([a.q_proj.bias, a.k_proj.bias, a.v_proj.bias], 0), a.out_proj, blk.mlp.fc1, blk.mlp.fc2)
+        P["w_kv"], P["w_kv_t"] = _both(wqkv[D:])
+        P["w_cls"], P["w_cls_t"] = _both(blk.cls_proj.weight)
+        P["b_cls"] = f32(blk.cls_proj.bias)
+        layers.append({**P, **_summary_weights(blk)})
     return dict(layers=layers, proj=_bf16(v.proj),     # cls_x = ln_post(x) @ proj (D,E): dx = d @ proj^T = gemm(d, W=proj)
                 summary_ver=model._summary_weight_versions())
 
 
 def refresh_vision_backward(model, bw):
-    """The summary-attention projections are the only trainable weights with bf16 copies: re-convert just those (in place)
-    after an optimizer step."""
+    """After an optimizer step: re-convert the summary-attention projections that changed, and nothing else."""
     cur = model._summary_weight_versions()
-    if cur == bw["summary_ver"]:
-        return
     for i, blk in enumerate(model.visual.blocks):
         if cur[i] != bw["summary_ver"][i]:
-            s = blk.summary_attn_layer
-            wsqkv = torch.cat([s.q_proj.weight, s.k_proj.weight, s.v_proj.weight], 0).detach()
-            P = bw["layers"][i]
-            P["w_sqkv"].copy_(_bf16(wsqkv)); P["w_sqkv_t"].copy_(_bf16(wsqkv.t()))
-            P["w_sout"].copy_(_bf16(s.out_proj.weight)); P["w_sout_t"].copy_(_bf16(s.out_proj.weight.detach().t()))
+            bw["layers"][i].update(_summary_weights(blk))
     bw["summary_ver"] = cur
 
 
@@ -230,179 +259,191 @@ def alloc_kept(model, B, T, device):
                 last_q=e(BT, D, dtype=h16), last_x1=e(BT, D), last_pre=e(BT, F, dtype=h16))
 
 
+def _vision_dims(model, B_in, T_in, dev):
+    """T_in frames per input clip; the blocks regroup the B_in*T_in frames by the MODEL's num_frames regardless
+    (vision_encoder_utils.py:160-162): inside the block loop (B, T) are (groups, num_frames), the head and the temporal
+    embedding keep the input's (B_in, T_in)."""
+    sh, T = model._shape, model.num_frames
+    B, n1 = B_in * T_in // T, (sh["size"] // sh["P"]) ** 2 + 1
+    return SimpleNamespace(B_in=B_in, T_in=T_in, B=B, T=T, BT=B * T, n1=n1, R=B * T * n1, SR=sh["G"] + 2 * B * T, D=sh["D"],
+                           H=sh["H"], F=sh["F"], E=sh["E"], G=sh["G"], NL=sh["layers"], dev=dev)
+
+
+def _vision_scratch(d, recompute):
+    """Every fixed-shape scratch tensor of the block loop, allocated once per backward call (stream order makes the reuse
+    from block to block safe).  Nothing in here may end up in the returned gradients: those are fresh tensors."""
+    b, f = (lambda *shape: new(d.dev, *shape)), (lambda *shape: new(d.dev, *shape, dtype=torch.float32))
+    BT, D, SR = d.BT, d.D, d.SR
+    s = _block_scratch(d.dev, d.R, D, d.F, recompute)
+    if recompute:
+        s.SIDEn, s.SIDEKV = b(SR, D), b(SR, 2 * D)
+    # prompt path forward (cls_proj, summary_ln, summary attention), then backward; part: per-frame partials of d K/V of the prompt rows
+    s.CP, s.CPn, s.SQKV, s.SMIX, s.SUMM = f(BT, D), b(BT, D), b(BT, 3 * D), b(BT, D), f(BT, D)
+    s.part, s.dSIDEn, s.dSIDE = f(BT * (d.G + d.T + 1), 2 * D), f(SR, D), f(SR, D)
+    s.dSMIX, s.dSQKV, s.dCPn, s.dCLS = b(BT, D), b(BT, 3 * D), f(BT, D), f(BT, D)
+    return s
+
+
+def _block_params(blk):
+    """This step's values of the block's LayerNorm affines and summary-attention biases (trainable ones among them, so
+    they are read per call, not packed)."""
+    a = blk.summary_attn_layer
+    return SimpleNamespace(ln=(f32(blk.norm1.weight), f32(blk.norm1.bias), f32(blk.norm2.weight), f32(blk.norm2.bias)),
+                           sln_g=f32(blk.summary_ln.weight), sln_b=f32(blk.summary_ln.bias),
+                           b_sqkv=f32(torch.cat([a.q_proj.bias, a.k_proj.bias, a.v_proj.bias], 0)), b_sout=f32(a.out_proj.bias))
+
+
+def _head_backward(model, bw, d, x_final, dcls_x):
+    """cls_x = mean_t(ln_post(x_cls) @ proj) (VitaCLIP_vision_encoder.py:126-128), in reverse: mean over T, proj^T, ln_post'
+    on the CLS rows.  -> dX [R, D] fp32, zero off the CLS rows."""
+    cls_idx = (torch.arange(d.BT, device=d.dev, dtype=torch.int32) * d.n1).contiguous()
+    dproj = (dcls_x.float() / d.T_in).unsqueeze(1).expand(d.B_in, d.T_in, d.E).reshape(d.BT, d.E).contiguous()
+    dclspost = new(d.dev, d.BT, d.D, dtype=torch.float32)
+    hip.gemm(hip.convert_h16(dproj, BWD), bw["proj"], None, dclspost, epilogue=hip.EPI_F32, prec=BWD)
+    dX = torch.zeros(d.R, d.D, dtype=torch.float32, device=d.dev)
+    hip.layernorm_backward(x_final, f32(model.visual.ln_post.weight), dclspost, dX, x_row_index=cls_idx, dx_row_index=cls_idx, rows=d.BT)
+    return dX
+
+
+def _prompt_recompute(P, prm, gp, lp, X0, d, s):
+    """Recompute the prompt ("side") path of a block (vision_encoder_utils.py:164-190): cls_proj of the CLS rows (s.CP),
+    summary_ln (s.CPn), the T-token summary attention (s.SQKV, s.SMIX) with its out_proj + residual (s.SUMM).
+    gp (G, D) / lp (T, D): the block's global / local prompts.  -> SIDE [SR, D] fp32, the rows every frame attends to
+    besides its own: [global prompts | local prompts + CP | summary tokens]."""
+    BT, D = d.BT, d.D
+    cls16 = hip.convert_h16(X0.view(BT, d.n1, D)[:, 0], BWD)
+    hip.gemm(cls16, P["w_cls"], P["b_cls"], s.CP, epilogue=hip.EPI_F32, prec=BWD)
+    hip.layernorm(s.CP, prm.sln_g, prm.sln_b, out16=s.CPn, prec=BWD)
+    hip.gemm(s.CPn, P["w_sqkv"], prm.b_sqkv, s.SQKV, epilogue=hip.EPI_H16, prec=BWD, scale_cols=D, scale=0.125)
+    hip.attention(*split3(s.SQKV), s.SMIX, batch=d.B, heads=d.H, n_q=d.T, n_kmain=d.T, prec=BWD)
+    hip.gemm(s.SMIX, P["w_sout"], prm.b_sout, s.SUMM, epilogue=hip.EPI_F32, prec=BWD, resid=s.CP)
+    return torch.cat([gp, (s.CP.view(d.B, d.T, D) + lp).view(BT, D), s.SUMM], 0).contiguous()
+
+
+def _main_activations(kept, i, cls_only, P, prm, X0, SIDE, d, s):
+    """-> (SIDEKV, qkv, X1, pre) of block i: the prompt rows' K/V, the main rows' q/k/v, the stream after the attention
+    branch and the fc1 pre-activation.  From what the forward kept (in its operand type; for a CLS-only last block X1 and
+    pre are the CLS rows' only), or recomputed from the block input X0 and SIDE with the forward kernels (bf16)."""
+    if kept is not None:
+        X1, pre = (kept["last_x1"], kept["last_pre"]) if cls_only else (kept["x1"][i], kept["pre"][i])
+        return kept["sidekv"][i], kept["qkv"][i], X1, pre
+    D = d.D
+    hip.layernorm(SIDE, prm.ln[0], prm.ln[1], out16=s.SIDEn, prec=BWD)
+    hip.gemm(s.SIDEn, P["w_kv"], P["b_qkv"][D:], s.SIDEKV, epilogue=hip.EPI_H16, prec=BWD)
+    _block_recompute(P, prm.ln, X0, s, batch=d.BT, heads=d.H, n_q=d.n1, n_kmain=d.n1,
+                     side_k=s.SIDEKV[:, :D], side_v=s.SIDEKV[:, D:], n_g=d.G, T=d.T, has_summary=True)
+    return s.SIDEKV, s.qkv, s.X1, s.pre
+
+
+def _cls_only_backward(P, ln2_g, dX, s, last_q, qkv, X1c, pre_c, act, **attn):
+    """The main-row backward of a kept last block: only the CLS rows carry a gradient (VitaCLIP_vision_encoder.py:126) -
+    MLP', out_proj' and the query side of attention' on B*T rows (last_q, X1c, pre_c: the CLS rows' queries, stream and
+    pre-activation); keys / values (and through them every row of the block input) in full.  Leaves s.dxn like
+    `_block_backward`."""
+    BT, D = last_q.shape
+    n1 = dX.shape[0] // BT
+    c = _block_scratch(dX.device, BT, D, pre_c.shape[1])
+    dXc = dX.view(BT, n1, D)[:, 0].contiguous()
+    hip.convert_h16(dXc, BWD, out=c.dx16)
+    _mlp_backward(P, ln2_g, dXc, c, X1c, pre_c, act)
+    dq_c = new(dX.device, BT, D)
+    hip.attention_backward(last_q, *split3(qkv)[1:], c.dmix, dq_c, *split3(s.dqkv)[1:], prec=BWD, q_scale=0.125, act_prec=act,
+                           n_q=1, q_batch_rows=1, **attn)
+    hip.gemm(s.dqkv[:, D:], P["w_kv_t"], None, s.dxn, epilogue=hip.EPI_F32, prec=BWD)          # [dK dV] . [Wk; Wv]
+    dxn_cls = s.dxn.view(BT, n1 * D)[:, :D]                                                     # CLS rows, stride n1*D
+    hip.gemm(dq_c, P["w_qkv_t"][:, :D], None, dxn_cls, epilogue=hip.EPI_F32, prec=BWD, resid=dxn_cls)   # + dQ . Wq
+    dX.view(BT, n1, D)[:, 0] = dXc
+
+
+def _prompt_backward(P, prm, i, SIDE, dsummary, dX, grads, dgp, d, s):
+    """The prompt rows' backward: sum the partials over the frames that share a row (global: all; local: the T frames of
+    the clip; summary: its own frame), then K/V projection^T, norm1', split into global / local / summary; summary
+    attention' with its weight and bias gradients, summary_ln', and cls_proj' back onto the CLS rows of dX.  dsummary: the
+    auxiliary head's gradient of the summary (last block only) or None.  Fills `grads` with block i's entries and dgp[i]."""
+    B, T, BT, D, G = d.B, d.T, d.BT, d.D, d.G
+    pv = s.part.view(B, T, G + T + 1, 2 * D)      # attention' wrote d K/V of the shared prompt rows as per-frame partials
+    dsidekv = torch.cat([pv[:, :, :G].sum(dim=(0, 1)), pv[:, :, G:G + T].sum(dim=1).reshape(BT, 2 * D),
+                         pv[:, :, G + T].reshape(BT, 2 * D)], 0).contiguous()
+    hip.gemm(hip.convert_h16(dsidekv, BWD), P["w_kv_t"], None, s.dSIDEn, epilogue=hip.EPI_F32, prec=BWD)
+    hip.layernorm_backward(SIDE, prm.ln[0], s.dSIDEn, s.dSIDE)
+    dgp[i] = s.dSIDE[:G]
+    dlocal, dSUMM = s.dSIDE[G:G + BT], s.dSIDE[G + BT:]
+    if dsummary is not None:
+        # summary = mean over T of the last block's summary tokens (VitaCLIP_vision_encoder.py:129-130)
+        dSUMM = dSUMM + (dsummary.float() / T).repeat_interleave(T, dim=0)
+    grads[f"blocks.{i}.local_prompts"] = dlocal.view(B, T, D).sum(0).unsqueeze(0)
+    dCP = (dlocal + dSUMM).contiguous()                      # local = lp + CP;  SUMM = CP + out_proj(...)
+    # ---- summary attention' (T tokens per clip) with parameter gradients
+    dSUMM16 = hip.convert_h16(dSUMM, BWD)
+    hip.gemm(dSUMM16, P["w_sout_t"], None, s.dSMIX, epilogue=hip.EPI_H16, prec=BWD)
+    grads[f"blocks.{i}.summary_attn_layer.out_proj.weight"] = _wgrad(dSUMM16, s.SMIX)
+    grads[f"blocks.{i}.summary_attn_layer.out_proj.bias"] = dSUMM.sum(0)
+    hip.attention_backward(*split3(s.SQKV), s.dSMIX, *split3(s.dSQKV), batch=B, heads=d.H, n=T, prec=BWD, q_scale=0.125)
+    dWs = _wgrad(s.dSQKV, s.CPn)
+    dbs = s.dSQKV.float().sum(0)
+    for k, nm in enumerate(("q_proj", "k_proj", "v_proj")):
+        grads[f"blocks.{i}.summary_attn_layer.{nm}.weight"] = dWs[k * D:(k + 1) * D]
+        grads[f"blocks.{i}.summary_attn_layer.{nm}.bias"] = dbs[k * D:(k + 1) * D]
+    hip.gemm(s.dSQKV, P["w_sqkv_t"], None, s.dCPn, epilogue=hip.EPI_F32, prec=BWD)
+    dg, db = torch.zeros(D, device=d.dev), torch.zeros(D, device=d.dev)
+    hip.layernorm_backward(s.CP, prm.sln_g, s.dCPn, dCP, accumulate=True, dgamma=dg, dbeta=db)
+    grads[f"blocks.{i}.summary_ln.weight"], grads[f"blocks.{i}.summary_ln.bias"] = dg, db
+    # ---- cls_proj' (frozen weight): back onto the CLS rows of the block input
+    hip.gemm(hip.convert_h16(dCP, BWD), P["w_cls_t"], None, s.dCLS, epilogue=hip.EPI_F32, prec=BWD)
+    dX.view(BT, d.n1, D)[:, 0] += s.dCLS
+
+
+def _embedding_backward(model, d, e0, dX):
+    """ln_pre' (in place on dX; e0 is the embedding output it normalised) and the temporal embedding
+    (VitaCLIP_vision_encoder.py:86-100,108-113): time_embed[t] is added to every token of frame t.  -> d time_embed."""
+    hip.layernorm_backward(e0, f32(model.visual.ln_pre.weight), dX, dX)
+    dte = dX.view(d.B_in, d.T_in, d.n1, d.D).sum(dim=(0, 2))
+    if d.T_in != d.T:   # nearest-resized time_embed (VitaCLIP_vision_encoder.py:91-95): row t of the resized table is row floor(t*T/T_in)
+        src = (torch.arange(d.T_in, device=d.dev) * d.T) // d.T_in
+        dte = torch.zeros(d.T, d.D, dtype=dte.dtype, device=d.dev).index_add_(0, src, dte)
+    return dte
+
+
 def vision_backward(model, saved, dcls_x, B, T, dsummary=None, kept=None):
     """d cls_x (B,E) [+ d summary (B,D), the auxiliary NTE head's input] -> {parameter name: gradient} for the trainable
     vision parameters.  `kept` (alloc_kept, filled by the forward) replaces the per-block recomputation of the main rows:
     activations are then in the forward's operand type (fp16 by default) while gradients stay bf16 - the attention
     backward converts K/V/Q as it stages them, the QuickGELU' epilogue decodes the pre-activation by its own flag."""
-    sh = model._shape
-    bw = model._pack_vision_backward()
-    D, H, F, E, G, NL = sh["D"], sh["H"], sh["F"], sh["E"], sh["G"], sh["layers"]
-    n1 = (sh["size"] // sh["P"]) ** 2 + 1
-    # T_in frames per input clip; the blocks regroup the B*T_in frames by the MODEL's num_frames regardless
-    # (vision_encoder_utils.py:160-162): inside the block loop (B, T) are (groups, num_frames), the head and the temporal
-    # embedding keep the input's (B_in, T_in)
-    B_in, T_in = B, T
-    T = model.num_frames
-    B = B_in * T_in // T
-    BT, R, SR = B * T, B * T * n1, G + 2 * B * T
-    dev = dcls_x.device
-    bf = torch.bfloat16
-    new = lambda *s, dtype=bf: torch.empty(*s, dtype=dtype, device=dev)
-    conv = lambda src, dst: hip.check(hip.load().gava_convert_h16(hip.ptr(src), hip.ptr(dst), src.numel(), BWD, hip.stream_ptr()), "convert")
-    v = model.visual
-    grads = {}
-    cls_idx = (torch.arange(BT, device=dev, dtype=torch.int32) * n1).contiguous()
-
-    # ---- head: cls_x = mean_t(ln_post(x_cls) @ proj)                          (VitaCLIP_vision_encoder.py:126-128)
-    dproj = (dcls_x.float() / T_in).unsqueeze(1).expand(B_in, T_in, E).reshape(BT, E).contiguous()
-    dclspost = new(BT, D, dtype=torch.float32)
-    hip.gemm(hip.convert_h16(dproj, BWD), bw["proj"], None, dclspost, epilogue=hip.EPI_F32, prec=BWD)
-    dX = torch.zeros(R, D, dtype=torch.float32, device=dev)
-    x_final = kept["x"][NL] if kept is not None else saved[NL + 1]
-    hip.layernorm_backward(x_final, v.ln_post.weight.detach().float().contiguous(), dclspost, dX,
-                           x_row_index=cls_idx, dx_row_index=cls_idx, rows=BT)
-
-    if kept is None:
-        xn, qkv_buf, mix, pre_buf, X1_buf = new(R, D), new(R, 3 * D), new(R, D), new(R, F), new(R, D, dtype=torch.float32)
-    dx16, dhid, dmix, dqkv = new(R, D), new(R, F), new(R, D), new(R, 3 * D)
-    dxn = new(R, D, dtype=torch.float32)
-    conv(dX, dx16)
+    bw, v = model._backward_pack("vision"), model.visual
+    d = _vision_dims(model, B, T, dcls_x.device)
+    if kept is not None:      # block inputs x[i] (x[NL]: the last block's output), embedding output, activations' storage type
+        xs, e0, act, last_q = kept["x"], kept["e0"], model.prec, kept.get("last_q")
+    else:
+        xs, e0, act, last_q = saved[1:], saved[0], BWD, None
+    NL, D, grads = d.NL, d.D, {}
+    dX = _head_backward(model, bw, d, xs[NL], dcls_x)
+    s = _vision_scratch(d, recompute=kept is None)
+    hip.convert_h16(dX, BWD, out=s.dx16)
     dgp = torch.zeros_like(v.global_prompts, dtype=torch.float32)
     for i in reversed(range(NL)):
-        P, blk = bw["layers"][i], v.blocks[i]
-        X0 = kept["x"][i] if kept is not None else saved[1 + i]
-        ACT = model.prec if kept is not None else BWD          # storage type of the activations used below
-        f32 = lambda p: p.detach().float().contiguous()
-        ln1_g, ln1_b, ln2_g, ln2_b = f32(blk.norm1.weight), f32(blk.norm1.bias), f32(blk.norm2.weight), f32(blk.norm2.bias)
-        sln_g, sln_b = f32(blk.summary_ln.weight), f32(blk.summary_ln.bias)
-        s = blk.summary_attn_layer
-        b_sqkv = f32(torch.cat([s.q_proj.bias, s.k_proj.bias, s.v_proj.bias], 0))
-        # ---- recompute: prompt ("side") path                                 (vision_encoder_utils.py:164-190)
-        cls16 = hip.convert_h16(X0.view(BT, n1, D)[:, 0].contiguous(), BWD)
-        CP = new(BT, D, dtype=torch.float32)
-        hip.gemm(cls16, P["w_cls"], P["b_cls"], CP, epilogue=hip.EPI_F32, prec=BWD)
-        CPn = new(BT, D)
-        hip.layernorm(CP, sln_g, sln_b, out16=CPn, prec=BWD)
-        SQKV = new(BT, 3 * D)
-        hip.gemm(CPn, P["w_sqkv"], b_sqkv, SQKV, epilogue=hip.EPI_H16, prec=BWD, scale_cols=D, scale=0.125)
-        SMIX = new(BT, D)
-        hip.attention(SQKV[:, :D], SQKV[:, D:2 * D], SQKV[:, 2 * D:], SMIX, batch=BT // T, heads=H, n_q=T, n_kmain=T, prec=BWD)
-        SUMM = new(BT, D, dtype=torch.float32)
-        hip.gemm(SMIX, P["w_sout"], f32(s.out_proj.bias), SUMM, epilogue=hip.EPI_F32, prec=BWD, resid=CP)
-        lp = blk.local_prompts.detach().float()[0]                                     # (T, D)
-        SIDE = torch.cat([v.global_prompts.detach().float()[i], (CP.view(B, T, D) + lp).view(BT, D), SUMM], 0).contiguous()
-        cls_only = kept is not None and i == NL - 1 and "last_q" in kept
+        P, blk, X0 = bw["layers"][i], v.blocks[i], xs[i]
+        prm = _block_params(blk)
+        cls_only = last_q is not None and i == NL - 1
+        SIDE = _prompt_recompute(P, prm, v.global_prompts.detach().float()[i], blk.local_prompts.detach().float()[0], X0, d, s)
+        SIDEKV, qkv, X1, pre = _main_activations(kept, i, cls_only, P, prm, X0, SIDE, d, s)
+        attn = dict(batch=d.BT, heads=d.H, n=d.n1, side_k=SIDEKV[:, :D], side_v=SIDEKV[:, D:], dside_k=s.part[:, :D],
+                    dside_v=s.part[:, D:], n_g=d.G, T=d.T, has_summary=True)
         if cls_only:
-            SIDEKV, qkv = kept["sidekv"][i], kept["qkv"][i]
-        elif kept is not None:
-            SIDEKV, qkv, X1, pre = kept["sidekv"][i], kept["qkv"][i], kept["x1"][i], kept["pre"][i]
+            _cls_only_backward(P, prm.ln[2], dX, s, last_q, qkv, X1, pre, act, **attn)
         else:
-            SIDEn = new(SR, D)
-            hip.layernorm(SIDE, ln1_g, ln1_b, out16=SIDEn, prec=BWD)
-            SIDEKV = new(SR, 2 * D)
-            hip.gemm(SIDEn, P["w_kv"], P["b_qkv"][D:], SIDEKV, epilogue=hip.EPI_H16, prec=BWD)
-            # ---- recompute: main rows
-            qkv, X1, pre = qkv_buf, X1_buf, pre_buf
-            hip.layernorm(X0, ln1_g, ln1_b, out16=xn, prec=BWD)
-            hip.gemm(xn, P["w_qkv"], P["b_qkv"], qkv, epilogue=hip.EPI_H16, prec=BWD, scale_cols=D, scale=0.125)
-            hip.attention(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], mix, batch=BT, heads=H, n_q=n1, n_kmain=n1, prec=BWD,
-                          side_k=SIDEKV[:, :D], side_v=SIDEKV[:, D:], n_g=G, T=T, has_summary=True)
-            hip.gemm(mix, P["w_out"], P["b_out"], X1, epilogue=hip.EPI_F32, prec=BWD, resid=X0)
-            hip.layernorm(X1, ln2_g, ln2_b, out16=xn, prec=BWD)
-            hip.gemm(xn, P["w_fc1"], P["b_fc1"], pre, epilogue=hip.EPI_H16, prec=BWD)
-        part = new(BT, G + T + 1, 2 * D, dtype=torch.float32)     # per-frame partials of the shared prompt rows
-        dside = part.view(BT * (G + T + 1), 2 * D)
-        if cls_only:
-            # last block: only the CLS rows carry a gradient (VitaCLIP_vision_encoder.py:126) - MLP', out_proj' and the
-            # query side of attention' on B*T rows; keys / values (and through them every row of the block input) in full
-            dXc = dX.view(BT, n1, D)[:, 0].contiguous()
-            dxc16 = hip.convert_h16(dXc, BWD)
-            dhid_c = new(BT, F)
-            hip.gemm(dxc16, P["w_fc2_t"], None, dhid_c, epilogue=hip.EPI_H16_QGELU_BWD, prec=BWD, aux=kept["last_pre"], aux_prec=ACT)
-            dxn_c = new(BT, D, dtype=torch.float32)
-            hip.gemm(dhid_c, P["w_fc1_t"], None, dxn_c, epilogue=hip.EPI_F32, prec=BWD)
-            hip.layernorm_backward(kept["last_x1"], ln2_g, dxn_c, dXc, accumulate=True, dx16=dxc16)
-            dmix_c, dq_c = new(BT, D), new(BT, D)
-            hip.gemm(dxc16, P["w_out_t"], None, dmix_c, epilogue=hip.EPI_H16, prec=BWD)
-            hip.attention_backward(kept["last_q"], qkv[:, D:2 * D], qkv[:, 2 * D:], dmix_c, dq_c, dqkv[:, D:2 * D], dqkv[:, 2 * D:],
-                                   batch=BT, heads=H, n=n1, prec=BWD, q_scale=0.125,
-                                   side_k=SIDEKV[:, :D], side_v=SIDEKV[:, D:], dside_k=dside[:, :D], dside_v=dside[:, D:],
-                                   n_g=G, T=T, has_summary=True, act_prec=ACT, n_q=1, q_batch_rows=1)
-            hip.gemm(dqkv[:, D:], P["w_kv_t"], None, dxn, epilogue=hip.EPI_F32, prec=BWD)          # [dK dV] . [Wk; Wv]
-            dxn_cls = dxn.view(BT, n1 * D)[:, :D]                                                     # CLS rows, stride n1*D
-            hip.gemm(dq_c, P["w_qkv_t"][:, :D], None, dxn_cls, epilogue=hip.EPI_F32, prec=BWD, resid=dxn_cls)   # + dQ . Wq
-            dX.view(BT, n1, D)[:, 0] = dXc
-        else:
-            # ---- MLP'                                                       (vision_encoder_utils.py:109-115,199)
-            #      (dx16 = bf16 copy of dX, written by the LayerNorm' that produced dX)
-            hip.gemm(dx16, P["w_fc2_t"], None, dhid, epilogue=hip.EPI_H16_QGELU_BWD, prec=BWD, aux=pre, aux_prec=ACT)   # fc2^T, gelu' fused
-            hip.gemm(dhid, P["w_fc1_t"], None, dxn, epilogue=hip.EPI_F32, prec=BWD)
-            hip.layernorm_backward(X1, ln2_g, dxn, dX, accumulate=True, dx16=dx16)
-            # ---- attention'                                                 (vision_encoder_utils.py:61-81,190-191)
-            hip.gemm(dx16, P["w_out_t"], None, dmix, epilogue=hip.EPI_H16, prec=BWD)
-            hip.attention_backward(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], dmix, dqkv[:, :D], dqkv[:, D:2 * D], dqkv[:, 2 * D:],
-                                   batch=BT, heads=H, n=n1, prec=BWD, q_scale=0.125,
-                                   side_k=SIDEKV[:, :D], side_v=SIDEKV[:, D:], dside_k=dside[:, :D], dside_v=dside[:, D:],
-                                   n_g=G, T=T, has_summary=True, act_prec=ACT)
-            hip.gemm(dqkv, P["w_qkv_t"], None, dxn, epilogue=hip.EPI_F32, prec=BWD)
-        # (norm1' of the main rows is applied at the end of the block, after the prompt path has added its share to
-        #  the CLS rows of dX: it also writes the bf16 copy of the finished dX for the next block)
-        # ---- prompt rows': sum the partials over the frames that share a row (global: all; local: the T frames of the
-        #      clip; summary: its own frame), then K/V projection^T, norm1', split into global / local / summary
-        pv = part.view(B, T, G + T + 1, 2 * D)
-        dsidekv = torch.cat([pv[:, :, :G].sum(dim=(0, 1)), pv[:, :, G:G + T].sum(dim=1).reshape(BT, 2 * D),
-                             pv[:, :, G + T].reshape(BT, 2 * D)], 0).contiguous()
-        dSIDEn = new(SR, D, dtype=torch.float32)
-        hip.gemm(hip.convert_h16(dsidekv, BWD), P["w_kv_t"], None, dSIDEn, epilogue=hip.EPI_F32, prec=BWD)
-        dSIDE = new(SR, D, dtype=torch.float32)
-        hip.layernorm_backward(SIDE, ln1_g, dSIDEn, dSIDE)
-        dgp[i] = dSIDE[:G]
-        dlocal, dSUMM = dSIDE[G:G + BT], dSIDE[G + BT:]
-        if dsummary is not None and i == NL - 1:
-            # summary = mean over T of the last block's summary tokens (VitaCLIP_vision_encoder.py:129-130)
-            dSUMM = dSUMM + (dsummary.float() / T).repeat_interleave(T, dim=0)
-        grads[f"blocks.{i}.local_prompts"] = dlocal.view(B, T, D).sum(0).unsqueeze(0)
-        dCP = (dlocal + dSUMM).contiguous()                      # local = lp + CP;  SUMM = CP + out_proj(...)
-        # ---- summary attention' (T tokens per clip) with parameter gradients
-        dSUMM16 = hip.convert_h16(dSUMM.contiguous(), BWD)
-        dSMIX = new(BT, D)
-        hip.gemm(dSUMM16, P["w_sout_t"], None, dSMIX, epilogue=hip.EPI_H16, prec=BWD)
-        grads[f"blocks.{i}.summary_attn_layer.out_proj.weight"] = _wgrad(dSUMM16, SMIX)
-        grads[f"blocks.{i}.summary_attn_layer.out_proj.bias"] = dSUMM.sum(0)
-        dSQKV = new(BT, 3 * D)
-        hip.attention_backward(SQKV[:, :D], SQKV[:, D:2 * D], SQKV[:, 2 * D:], dSMIX, dSQKV[:, :D], dSQKV[:, D:2 * D], dSQKV[:, 2 * D:],
-                               batch=BT // T, heads=H, n=T, prec=BWD, q_scale=0.125)
-        dWs = _wgrad(dSQKV, CPn)
-        dbs = dSQKV.float().sum(0)
-        for k, nm in enumerate(("q_proj", "k_proj", "v_proj")):
-            grads[f"blocks.{i}.summary_attn_layer.{nm}.weight"] = dWs[k * D:(k + 1) * D]
-            grads[f"blocks.{i}.summary_attn_layer.{nm}.bias"] = dbs[k * D:(k + 1) * D]
-        dCPn = new(BT, D, dtype=torch.float32)
-        hip.gemm(dSQKV, P["w_sqkv_t"], None, dCPn, epilogue=hip.EPI_F32, prec=BWD)
-        dg, db = torch.zeros(D, device=dev), torch.zeros(D, device=dev)
-        hip.layernorm_backward(CP, sln_g, dCPn, dCP, accumulate=True, dgamma=dg, dbeta=db)
-        grads[f"blocks.{i}.summary_ln.weight"], grads[f"blocks.{i}.summary_ln.bias"] = dg, db
-        # ---- cls_proj' (frozen weight): back onto the CLS rows of the block input
-        dCLS = new(BT, D, dtype=torch.float32)
-        hip.gemm(hip.convert_h16(dCP, BWD), P["w_cls_t"], None, dCLS, epilogue=hip.EPI_F32, prec=BWD)
-        dX.view(BT, n1, D)[:, 0] += dCLS
-        hip.layernorm_backward(X0, ln1_g, dxn, dX, accumulate=True, dx16=dx16)
+            _block_backward(P, prm.ln[2], dX, s, X1, pre, qkv, act, **attn)
+        _prompt_backward(P, prm, i, SIDE, dsummary if i == NL - 1 else None, dX, grads, dgp, d, s)
+        # norm1' of the main rows is applied at the end of the block, after the prompt path has added its share to
+        # the CLS rows of dX: it also writes the bf16 copy of the finished dX for the next block
+        hip.layernorm_backward(X0, prm.ln[0], s.dxn, dX, accumulate=True, dx16=s.dx16)
     grads["global_prompts"] = dgp
-    # ---- ln_pre' and the temporal embedding (VitaCLIP_vision_encoder.py:86-100,108-113): time_embed[t] is added to
-    #      every token of frame t
-    hip.layernorm_backward(kept["e0"] if kept is not None else saved[0], v.ln_pre.weight.detach().float().contiguous(), dX, dX)
-    dte = dX.view(B_in, T_in, n1, D).sum(dim=(0, 2))
-    if T_in != T:   # nearest-resized time_embed (VitaCLIP_vision_encoder.py:91-95): row t of the resized table is row floor(t*T/T_in)
-        src = (torch.arange(T_in, device=dev) * T) // T_in
-        dte = torch.zeros(T, D, dtype=dte.dtype, device=dev).index_add_(0, src, dte)
-    grads["time_embed"] = dte
+    grads["time_embed"] = _embedding_backward(model, d, e0, dX)
     return grads
 
 
 class VisionTowerFn(torch.autograd.Function):
     """cls_x = f(x; prompt parameters) with the HIP vision tower in both directions.  `params` are the trainable vision
-    parameters in `_vision_trainables` order (they enter only so that autograd routes their gradients).
+    parameters in `VitaCLIP._vision_trainables` order (they enter only so that autograd routes their gradients).
     clips: None, or the uint8 source of VitaCLIP.forward_frames (encode_video's `clips`; x is then the descriptor tensor).
     Either way the backward starts from what the forward kept (the embedding output and the blocks' activations, or in
     recompute mode the fp32 input of every block): the input is read by the forward's patch embedding only, so neither the
@@ -435,7 +476,7 @@ class VisionTowerFn(torch.autograd.Function):
         g = vision_backward(model, saved, dcls_x.contiguous(), *fctx.BT, dsummary=dsummary, kept=kept)
         fctx.kept = None      # release the activation buffers with the graph
         out = []
-        for name, p in _vision_trainables(model):
+        for name, p in model._vision_trainables():
             gi = g.get(name)
             out.append(gi.reshape(p.shape).to(p.dtype) if (gi is not None and p.requires_grad) else None)
         return (None, None, None, *out)

@@ -315,6 +315,41 @@ def test_gradients_match_reference_tiny(golden_dir, keep):
     _check_against_reference_grads(m, gold)
 
 
+@pytest.mark.parametrize("keep", [True, False])
+def test_second_backward_leaves_the_first_gradients_alone_and_repeats_them(keep):
+    """The backward's scratch is allocated per call and reused from block to block: no gradient it returns may alias
+    it.  Hold the first run's .grad tensors, run forward + backward again on the same input, and the held tensors still
+    equal their clones bit for bit.  The second run repeats the first bit for bit, except summary_ln.{weight,bias}:
+    gava_layernorm_backward accumulates those with fp32 atomics, whose order varies (B*T = 8 rows: reordering noise is
+    ~1e-7 relative, a wrong buffer is O(1)) - 1e-5 norm-wise."""
+    m = VitaCLIP(**model_kwargs(TINY, CLASSES_3))
+    m.load_state_dict(synth_torch_state(TINY, 3), strict=True)
+    m = m.cuda().train()
+    if not keep:
+        m.keep_activation_bytes = 0
+    x = torch.from_numpy(synth.synth_clip(2, TINY.num_frames, TINY.input_size)).cuda()
+    w = torch.randn(2, 3, generator=torch.Generator().manual_seed(3)).cuda()
+
+    def run():
+        for p in m.parameters():
+            p.grad = None
+        (m(x)[0] * w).sum().backward()
+        return {n: p.grad for n, p in m.named_parameters() if p.grad is not None}
+
+    held = run()
+    clones = {n: g.clone() for n, g in held.items()}
+    assert any("summary_attn_layer" in n for n in held) and "visual.time_embed" in held and "prompt_learner.ctx" in held
+    again = run()
+    torch.cuda.synchronize()
+    assert set(again) == set(held)
+    for n, g in held.items():
+        assert torch.equal(g, clones[n]), f"{n}: the first run's gradient changed under the second backward"
+        if ".summary_ln." in n:
+            assert rel(again[n], g) <= 1e-5, (n, rel(again[n], g))
+        else:
+            assert torch.equal(again[n], g), (n, rel(again[n], g))
+
+
 def test_gradients_match_reference_with_auxiliary_heads(golden_dir):
     """add_nte + use_support_memory (VitaCLIP_model.py:311-398): the NTE head hangs off `summary`, the memory head off
     `text_features`; their outputs and every gradient (including sum_proj / tf_project / memory_project, handled by
