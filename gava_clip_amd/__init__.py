@@ -13,4 +13,7 @@ def __getattr__(name):  # lazy: importing the package must not need torch/HIP
     if name == "TrainCriterion":
         from .training import TrainCriterion
         return TrainCriterion
+    if name == "AuxCriterion":
+        from .training import AuxCriterion
+        return AuxCriterion
     raise AttributeError(name)

@@ -107,6 +107,12 @@ static __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+static __device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
 static __device__ __forceinline__ float quick_gelu(float x) {
   // x * sigmoid(1.702 x)  (VitaCLIP_vision_encoder_utils.py:18-20); exp(-1.702 x) = exp2(x * (-1.702 log2 e)):
   // one multiply in front of v_exp_f32 instead of the two that __expf(-1.702f * x) compiles to

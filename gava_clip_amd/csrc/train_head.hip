@@ -7,12 +7,6 @@
 
 namespace {
 
-static __device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 static __device__ __forceinline__ int clamp_label(long y, int C) { return (int)(y < 0 ? 0 : (y >= C ? C - 1 : y)); }
 
 // ---- criterion ----------------------------------------------------------------------------------------------------------------

@@ -27,7 +27,11 @@ EXPORTS = ["gava_abi_version", "gava_gemm", "gava_layernorm", "gava_attention",
            "gava_gemm_aligned_walk", "gava_vision_pair_stream", "gava_struct_sizes", "gava_clip_geometry_box",
            "gava_preprocess_clips", "gava_clip_geometry_view", "gava_view_scores",
            "gava_train_criterion", "gava_train_criterion_backward", "gava_train_head", "gava_train_head_backward",
-           "gava_train_struct_sizes"]
+           "gava_train_struct_sizes",
+           "gava_nte_head", "gava_nte_head_backward", "gava_memory_head", "gava_memory_head_backward",
+           "gava_memory_head_backward_workspace_floats", "gava_nte_head_backward_workspace_floats",
+           "gava_sigmoid_criterion", "gava_sigmoid_criterion_backward", "gava_nte_diag_loss", "gava_nte_diag_loss_backward",
+           "gava_aux_struct_sizes"]
 
 _vp, _fp, _ip = C.c_void_p, C.c_void_p, C.c_void_p  # all device pointers travel as void*
 
@@ -151,6 +155,38 @@ class TrainHeadArgs(C.Structure):
                 ("video_norm", _fp), ("video_inv", _fp), ("text_norm", _fp), ("text_inv", _fp), ("class_mean", _fp),
                 ("dlogits", _fp), ("dtext_features", _fp),
                 ("dvideo", _fp), ("dtext", _fp), ("dlogit_scale", _fp), ("dlogit_bias", _fp), ("workspace", _fp)]
+
+
+class NteHeadArgs(C.Structure):
+    _fields_ = [("summary", _fp), ("weight", _fp), ("bias", _fp), ("video_nte", _fp), ("logit_scale", _fp),
+                ("B", C.c_int), ("D", C.c_int), ("E", C.c_int), ("K", C.c_int),
+                ("logits_vm", _fp),
+                ("sp_norm", _fp), ("sp_inv", _fp), ("nte_mean", _fp), ("valid", _fp), ("sim", _fp), ("lm", _fp),
+                ("row_lse", _fp), ("col_lse", _fp),
+                ("dlogits", _fp), ("dsummary", _fp), ("dweight", _fp), ("dbias", _fp), ("dlogit_scale", _fp), ("workspace", _fp)]
+
+
+class MemoryHeadArgs(C.Structure):
+    _fields_ = [("memory", _fp), ("text_features", _fp), ("tf_w1", _fp), ("tf_b1", _fp), ("tf_w2", _fp), ("tf_b2", _fp),
+                ("mem_params", _vp), ("logit_scale", _fp), ("logit_bias", _fp),
+                ("M", C.c_int), ("S", C.c_int), ("C", C.c_int), ("E", C.c_int),
+                ("logits_mt", _fp),
+                ("mem_mean", _fp), ("mem_h", _fp), ("mem_z", _fp), ("mem_inv", _fp), ("tf_h", _fp), ("tf_u", _fp), ("tf_inv", _fp),
+                ("cosine", _fp), ("lse", _fp),
+                ("dlogits", _fp), ("dmem_w1", _fp), ("dmem_b1", _fp), ("dmem_w2", _fp), ("dmem_b2", _fp),
+                ("dtf_w1", _fp), ("dtf_b1", _fp), ("dtf_w2", _fp), ("dtf_b2", _fp),
+                ("dlogit_scale", _fp), ("dlogit_bias", _fp), ("dtext_features", _fp), ("workspace", _fp)]
+
+
+class SigmoidCriterionArgs(C.Structure):
+    _fields_ = [("logits", _fp), ("ld_logits", C.c_int64), ("labels", _ip),
+                ("M", C.c_int), ("C", C.c_int), ("use_focal", C.c_int),
+                ("alpha", C.c_float), ("gamma", C.c_float), ("scale", C.c_float),
+                ("loss", _fp), ("per_sample", _fp), ("grad_loss", _fp), ("dlogits", _fp), ("ld_dlogits", C.c_int64)]
+
+
+class NteDiagArgs(C.Structure):
+    _fields_ = [("logits_vm", _fp), ("B", C.c_int), ("weight", C.c_float), ("loss", _fp), ("grad_loss", _fp), ("dlogits_vm", _fp)]
 
 
 class PatchifyArgs(C.Structure):
@@ -289,6 +325,25 @@ def load():
     if lib.gava_train_struct_sizes(sizes, len(train_mirrors)) != len(train_mirrors):
         raise GavaError("libgava_hip.so and gava_clip_amd/hip.py disagree on the number of training-head ABI structs")
     for cls, sz in zip(train_mirrors, sizes):
+        if C.sizeof(cls) != sz:
+            raise GavaError(f"ctypes mirror {cls.__name__} is {C.sizeof(cls)} bytes, the library's struct {sz}: gava_clip_amd/hip.py is out of "
+                            f"step with include/gava_hip.h")
+    # the auxiliary heads' structs, the same way
+    aux_mirrors = [NteHeadArgs, MemoryHeadArgs, SigmoidCriterionArgs, NteDiagArgs]
+    for names, cls in ((("gava_nte_head", "gava_nte_head_backward"), NteHeadArgs),
+                       (("gava_memory_head", "gava_memory_head_backward"), MemoryHeadArgs),
+                       (("gava_sigmoid_criterion", "gava_sigmoid_criterion_backward"), SigmoidCriterionArgs),
+                       (("gava_nte_diag_loss", "gava_nte_diag_loss_backward"), NteDiagArgs)):
+        for name in names:
+            getattr(lib, name).argtypes, getattr(lib, name).restype = [C.POINTER(cls), _vp], C.c_int
+    lib.gava_nte_head_backward_workspace_floats.argtypes = [C.c_int, C.c_int]
+    lib.gava_nte_head_backward_workspace_floats.restype = C.c_size_t
+    lib.gava_memory_head_backward_workspace_floats.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.gava_memory_head_backward_workspace_floats.restype = C.c_size_t
+    lib.gava_aux_struct_sizes.argtypes, lib.gava_aux_struct_sizes.restype = [C.POINTER(C.c_size_t), C.c_int], C.c_int
+    if lib.gava_aux_struct_sizes(sizes, len(aux_mirrors)) != len(aux_mirrors):
+        raise GavaError("libgava_hip.so and gava_clip_amd/hip.py disagree on the number of auxiliary-head ABI structs")
+    for cls, sz in zip(aux_mirrors, sizes):
         if C.sizeof(cls) != sz:
             raise GavaError(f"ctypes mirror {cls.__name__} is {C.sizeof(cls)} bytes, the library's struct {sz}: gava_clip_amd/hip.py is out of "
                             f"step with include/gava_hip.h")
@@ -694,3 +749,204 @@ def train_head_backward(kept, dlogits, dtext_features=None):
     with torch.cuda.device(dev):
         check(load().gava_train_head_backward(C.byref(a), stream_ptr(dev)), "gava_train_head_backward")
     return dvideo, dtext, dls, dlb
+
+
+# ---- auxiliary heads and their loss terms (gava_nte_head*, gava_memory_head*, gava_sigmoid_criterion*, gava_nte_diag_loss*) ------
+
+def _require(ok, message):
+    """A caller's input is refused with GavaError, whatever the interpreter's optimisation level."""
+    if not ok:
+        raise GavaError(message)
+
+
+def _dev32(t, what):
+    """A device tensor as fp32, contiguous and 16-byte aligned (converted / copied only when it is not); CPU tensors are refused."""
+    if not (torch.is_tensor(t) and t.is_cuda):
+        raise GavaError(f"{what} must be a tensor on the HIP device: the auxiliary heads have no CPU fallback")
+    t = t.detach()
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        t = t.float().contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+_NTE_KEPT = ("sp_norm", "sp_inv", "nte_mean", "valid", "sim", "lm", "row_lse", "col_lse")
+
+
+def _nte_args(kept):
+    a = NteHeadArgs()
+    for k in ("summary", "weight", "bias", "video_nte", "logit_scale", "logits_vm") + _NTE_KEPT:
+        setattr(a, k, ptr(kept.get(k)))
+    a.B, a.D, a.E, a.K = kept["B"], kept["D"], kept["E"], kept["K"]
+    return a
+
+
+def nte_head(summary, weight, bias, video_nte, logit_scale):
+    """Forward of the video<->NTE head (gava_nte_head; the formulas are in include/gava_hip.h): summary [B, D], sum_proj's weight
+    [E, D] and bias [E], video_nte [B, K, E], logit_scale (one element, on the device) -> dict with logits_vm [B, B] and what
+    nte_head_backward reuses.  Five launches, no sync."""
+    summary, weight, bias, video_nte = _dev32(summary, "summary"), _dev32(weight, "weight"), _dev32(bias, "bias"), _dev32(video_nte, "video_nte")
+    _require(summary.dim() == 2 and weight.dim() == 2, "nte_head: summary and weight must have two dimensions")
+    (B, D), (E, D2) = summary.shape, weight.shape
+    _require(D2 == D and video_nte.dim() == 3 and video_nte.shape[0] == B and video_nte.shape[2] == E and tuple(bias.shape) == (E,),
+             f"nte_head: summary {tuple(summary.shape)}, weight {tuple(weight.shape)}, bias {tuple(bias.shape)} and video_nte "
+             f"{tuple(video_nte.shape)} do not fit [B, D], [E, D], [E], [B, K, E]")
+    dev = summary.device
+    new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+    kept = dict(B=B, D=D, E=E, K=video_nte.shape[1], summary=summary, weight=weight, logit_scale=_dev32(logit_scale, "logit_scale").reshape(1),
+                logits_vm=new(B, B), sp_norm=new(B, E), sp_inv=new(B), nte_mean=new(B, E), valid=new(B), sim=new(B, B), lm=new(B, B),
+                row_lse=new(B), col_lse=new(B))
+    a = _nte_args(dict(kept, bias=bias, video_nte=video_nte))
+    with torch.cuda.device(dev):
+        check(load().gava_nte_head(C.byref(a), stream_ptr(dev)), "gava_nte_head")
+    return kept
+
+
+def nte_head_backward(kept, dlogits):
+    """-> (dsummary [B, D], dweight [E, D], dbias [E], dlogit_scale [1]) from nte_head's dict and d logits_vm [B, B]."""
+    B, D, E = kept["B"], kept["D"], kept["E"]
+    dlogits = _dev32(dlogits, "dlogits")
+    _require(tuple(dlogits.shape) == (B, B), f"nte_head_backward: d logits_vm is {tuple(dlogits.shape)}, the forward's batch was {B}")
+    dev = dlogits.device
+    new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+    dsummary, dweight, dbias, dls = new(B, D), new(E, D), new(E), new(1)
+    ws = new(load().gava_nte_head_backward_workspace_floats(B, E))
+    a = _nte_args(kept)
+    a.dlogits, a.dsummary, a.dweight, a.dbias, a.dlogit_scale, a.workspace = ptr(dlogits), ptr(dsummary), ptr(dweight), ptr(dbias), ptr(dls), ptr(ws)
+    with torch.cuda.device(dev):
+        check(load().gava_nte_head_backward(C.byref(a), stream_ptr(dev)), "gava_nte_head_backward")
+    return dsummary, dweight, dbias, dls
+
+
+_MEM_KEPT = ("mem_mean", "mem_h", "mem_z", "mem_inv", "tf_h", "tf_u", "tf_inv", "cosine", "lse")
+
+
+def pointer_table(params, device):
+    """Device int64 tensor of the data pointers of `params` (fp32, contiguous, 16-byte aligned device tensors): the mem_params
+    table of gava_memory_head.  The caller keeps `params` alive and rebuilds the table when a pointer changes."""
+    for p in params:
+        if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.data_ptr() % 16 == 0):
+            raise GavaError("memory_project's parameters must be fp32, contiguous, 16-byte aligned tensors on the HIP device")
+    return torch.tensor([p.data_ptr() for p in params], dtype=torch.int64).to(device)
+
+
+def _memory_args(kept):
+    a = MemoryHeadArgs()
+    for k in ("memory", "text_features", "tf_w1", "tf_b1", "tf_w2", "tf_b2", "mem_params", "logit_scale", "logit_bias", "logits_mt") + _MEM_KEPT:
+        setattr(a, k, ptr(kept.get(k)))
+    a.M, a.S, a.C, a.E = kept["M"], kept["S"], kept["C"], kept["E"]
+    return a
+
+
+def memory_head(memory, text_features, tf_params, mem_table, logit_scale, logit_bias=None):
+    """Forward of the support-memory head (gava_memory_head): memory [M, S, E], text_features [C, E], tf_params = tf_project's
+    (W1, b1, W2, b2), mem_table = pointer_table of memory_project's parameters in class order (4 per class), logit_scale and
+    logit_bias one-element device tensors -> dict with logits_mt [M, C] and what memory_head_backward reuses.  Six launches."""
+    memory, text_features = _dev32(memory, "memory"), _dev32(text_features, "text_features")
+    tf_params = [_dev32(p, "tf_project") for p in tf_params]
+    _require(memory.dim() == 3 and text_features.dim() == 2 and text_features.shape[1] == memory.shape[2],
+             f"memory_head: memory {tuple(memory.shape)} and text_features {tuple(text_features.shape)} do not fit [M, S, E], [C, E]")
+    M, S, E = memory.shape
+    Cn = text_features.shape[0]
+    H1, H2 = E // 4, E // 8
+    _require(torch.is_tensor(mem_table) and mem_table.is_cuda and mem_table.dtype == torch.int64,
+             "memory_head: mem_table must be a device int64 tensor (hip.pointer_table)")
+    _require(mem_table.numel() == 4 * Cn, f"memory_head: text_features has {Cn} classes, the table of memory_project's parameters "
+                                          f"{mem_table.numel() // 4} (4 pointers per class)")
+    _require(len(tf_params) == 4 and [tuple(p.shape) for p in tf_params] == [(H1, E), (H1,), (H2, H1), (H2,)],
+             f"memory_head: tf_project's parameters must be [{H1}, {E}], [{H1}], [{H2}, {H1}], [{H2}]")
+    dev = memory.device
+    new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+    kept = dict(M=M, S=S, C=Cn, E=E, text_features=text_features, tf_w1=tf_params[0], tf_b1=tf_params[1], tf_w2=tf_params[2],
+                tf_b2=tf_params[3], mem_params=mem_table, logit_scale=_dev32(logit_scale, "logit_scale").reshape(1),
+                logit_bias=_dev32(logit_bias, "logit_bias").reshape(1) if logit_bias is not None else None,
+                logits_mt=new(M, Cn), mem_mean=new(M, E), mem_h=new(Cn, M, H1), mem_z=new(Cn, M, H2), mem_inv=new(M, Cn),
+                tf_h=new(Cn, H1), tf_u=new(Cn, H2), tf_inv=new(Cn), cosine=new(M, Cn), lse=new(M))
+    a = _memory_args(dict(kept, memory=memory))
+    with torch.cuda.device(dev):
+        check(load().gava_memory_head(C.byref(a), stream_ptr(dev)), "gava_memory_head")
+    return kept
+
+
+def memory_head_backward(kept, dlogits, want_dtext=True):
+    """-> dict(dmem_w1 [C, H1, E], dmem_b1 [C, H1], dmem_w2 [C, H2, H1], dmem_b2 [C, H2], dtf_w1, dtf_b1, dtf_w2, dtf_b2,
+    dlogit_scale [1], dlogit_bias [1] or None, dtext_features [C, E] or None) from memory_head's dict and d logits_mt [M, C]."""
+    M, Cn, E = kept["M"], kept["C"], kept["E"]
+    H1, H2 = E // 4, E // 8
+    dlogits = _dev32(dlogits, "dlogits")
+    _require(tuple(dlogits.shape) == (M, Cn), f"memory_head_backward: d logits_mt is {tuple(dlogits.shape)}, the forward's was {(M, Cn)}")
+    dev = dlogits.device
+    new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+    out = dict(dmem_w1=new(Cn, H1, E), dmem_b1=new(Cn, H1), dmem_w2=new(Cn, H2, H1), dmem_b2=new(Cn, H2),
+               dtf_w1=new(H1, E), dtf_b1=new(H1), dtf_w2=new(H2, H1), dtf_b2=new(H2), dlogit_scale=new(1),
+               dlogit_bias=new(1) if kept["logit_bias"] is not None else None,
+               dtext_features=new(Cn, E) if want_dtext else None)
+    ws = new(load().gava_memory_head_backward_workspace_floats(M, Cn, E))
+    a = _memory_args(kept)
+    a.dlogits, a.workspace = ptr(dlogits), ptr(ws)
+    for k, v in out.items():
+        setattr(a, k, ptr(v))
+    with torch.cuda.device(dev):
+        check(load().gava_memory_head_backward(C.byref(a), stream_ptr(dev)), "gava_memory_head_backward")
+    return out
+
+
+def _sigmoid_args(logits, labels, use_focal, alpha, gamma, scale):
+    _require(torch.is_tensor(logits) and logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2
+             and (logits.shape[1] == 1 or logits.stride(1) == 1), "logits must be device fp32 [M, C] with a contiguous class dimension")
+    M, Cn = logits.shape
+    _require(labels.is_cuda and labels.dtype == torch.int64 and labels.is_contiguous() and tuple(labels.shape) == (M,),
+             f"labels must be device int64 [{M}], contiguous")
+    a = SigmoidCriterionArgs()
+    a.logits, a.ld_logits, a.labels = ptr(logits), (logits.stride(0) if M > 1 else max(logits.stride(0), Cn)), ptr(labels)
+    a.M, a.C, a.use_focal, a.alpha, a.gamma, a.scale = M, Cn, int(use_focal), alpha, gamma, scale
+    return a
+
+
+def sigmoid_criterion(logits, labels, *, use_focal=False, alpha=0.25, gamma=2.0, scale=1.0):
+    """Mean over the samples of the sigmoid (focal) loss (gava_sigmoid_criterion): logits device fp32 [M, C], labels device int64
+    [M] -> dict(loss (0-dim), per_sample [M], labels).  Soft targets are refused.  Two launches, no sync."""
+    if not torch.is_tensor(labels) or labels.is_floating_point() or labels.dim() != 1:
+        raise GavaError("gava_sigmoid_criterion takes integer class labels [M]; soft targets are not supported")
+    labels = labels.to(device=logits.device, dtype=torch.int64).contiguous()
+    a = _sigmoid_args(logits, labels, use_focal, alpha, gamma, scale)
+    dev = logits.device
+    out = dict(loss=torch.empty((), dtype=torch.float32, device=dev), per_sample=torch.empty(logits.shape[0], dtype=torch.float32, device=dev),
+               labels=labels)
+    a.loss, a.per_sample = ptr(out["loss"]), ptr(out["per_sample"])
+    with torch.cuda.device(dev):
+        check(load().gava_sigmoid_criterion(C.byref(a), stream_ptr(dev)), "gava_sigmoid_criterion")
+    return out
+
+
+def sigmoid_criterion_backward(logits, labels, grad_loss, *, use_focal=False, alpha=0.25, gamma=2.0, scale=1.0):
+    """dlogits [M, C] of sigmoid_criterion's loss; grad_loss: the upstream gradient, a device fp32 scalar."""
+    _require(grad_loss.is_cuda and grad_loss.dtype == torch.float32 and grad_loss.numel() == 1, "grad_loss must be one device fp32 value")
+    a = _sigmoid_args(logits, labels, use_focal, alpha, gamma, scale)
+    dlogits = torch.empty(logits.shape, dtype=torch.float32, device=logits.device)
+    a.grad_loss, a.dlogits, a.ld_dlogits = ptr(grad_loss), ptr(dlogits), logits.shape[1]
+    with torch.cuda.device(logits.device):
+        check(load().gava_sigmoid_criterion_backward(C.byref(a), stream_ptr(logits.device)), "gava_sigmoid_criterion_backward")
+    return dlogits
+
+
+def nte_diag_loss(logits_vm, weight=1.0):
+    """-weight * mean of the diagonal of logits_vm [B, B] (device fp32, contiguous) -> 0-dim device tensor.  One launch."""
+    _require(torch.is_tensor(logits_vm) and logits_vm.is_cuda and logits_vm.dtype == torch.float32 and logits_vm.dim() == 2
+             and logits_vm.shape[0] == logits_vm.shape[1] and logits_vm.is_contiguous(), "logits_vm must be device fp32 [B, B], contiguous")
+    loss = torch.empty((), dtype=torch.float32, device=logits_vm.device)
+    a = NteDiagArgs()
+    a.logits_vm, a.B, a.weight, a.loss = ptr(logits_vm), logits_vm.shape[0], weight, ptr(loss)
+    with torch.cuda.device(logits_vm.device):
+        check(load().gava_nte_diag_loss(C.byref(a), stream_ptr(logits_vm.device)), "gava_nte_diag_loss")
+    return loss
+
+
+def nte_diag_loss_backward(B, grad_loss, weight=1.0):
+    """d logits_vm [B, B] of nte_diag_loss; grad_loss: a device fp32 scalar."""
+    _require(grad_loss.is_cuda and grad_loss.dtype == torch.float32 and grad_loss.numel() == 1, "grad_loss must be one device fp32 value")
+    d = torch.empty(B, B, dtype=torch.float32, device=grad_loss.device)
+    a = NteDiagArgs()
+    a.B, a.weight, a.grad_loss, a.dlogits_vm = B, weight, ptr(grad_loss), ptr(d)
+    with torch.cuda.device(d.device):
+        check(load().gava_nte_diag_loss_backward(C.byref(a), stream_ptr(d.device)), "gava_nte_diag_loss_backward")
+    return d

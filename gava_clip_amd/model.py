@@ -336,6 +336,18 @@ class _HipHost:
     """Weight packing and tower launches on libgava_hip.so, shared by VitaCLIP and by stand-alone encoders.  Expects
     `visual` and / or `textual` attributes (parameter containers), `num_frames`, and the nn.Module parameter iterators."""
 
+    # the auxiliary heads' route, refused where it is set (train_head, its sibling, is read on every training forward and is
+    # checked there; this one may not be read for many calls - the heads run only when memory / video_nte are passed)
+    @property
+    def aux_heads(self):
+        return self._aux_heads
+
+    @aux_heads.setter
+    def aux_heads(self, route):
+        if route not in ("torch", "hip"):
+            raise hip.GavaError(f"aux_heads must be 'torch' or 'hip', got {route!r}")
+        self._aux_heads = route
+
     def _hip_init(self, shape, operand_dtype=None):
         operand_dtype = operand_dtype or os.environ.get("GAVA_PREC", "fp16")
         self.prec, self.w_lo = self._parse_operand_dtype(operand_dtype)
@@ -363,6 +375,9 @@ class _HipHost:
         # the similarity head under autograd: "torch" = traced torch ops (_train_head), "hip" = training.HeadFn (gava_train_head)
         self.train_head = os.environ.get("GAVA_TRAIN_HEAD", "torch")
         self._head_offsets = (None, None)
+        # the auxiliary NTE and support-memory heads: "torch" = traced torch ops, "hip" = training.NteHeadFn / MemoryHeadFn
+        self.aux_heads = os.environ.get("GAVA_AUX_HEADS", "torch")
+        self._mem_table = (None, None)
         self._text_stream = None
         self._text_cache = None
         self.gather_across_ranks = True     # RCCL all-gather of clip embeddings when world_size > 1
@@ -998,6 +1013,18 @@ class VitaCLIP(nn.Module, _HipHost):
         return [(n, p) for n, p in self.visual.named_parameters()
                 if ("summary" in n or "local" in n or "global" in n or "time_embed" in n)]
 
+    def _memory_head_hip(self, memory, text_features):
+        """The support-memory head as one autograd node (training.MemoryHeadFn; aux_heads = "hip").  memory_project's
+        parameters reach the kernels through a device table of their pointers, rebuilt only when a pointer changes."""
+        from .training import MemoryHeadFn
+        params = list(self.tf_project.parameters()) + [q for mp in self.memory_project for q in mp.parameters()]
+        if not torch.is_tensor(memory) or not memory.is_cuda:
+            raise hip.GavaError("memory must be a tensor on the HIP device: the auxiliary heads have no CPU fallback")
+        key = (tuple(q.data_ptr() for q in params[4:]), memory.device)
+        if self._mem_table[0] != key:
+            self._mem_table = (key, hip.pointer_table(params[4:], memory.device))
+        return MemoryHeadFn.apply(memory, text_features, self.logit_scale_mt, self.logit_bias_mt, self._mem_table[1], *params)
+
     def _train_head(self, video, text, summary, desc_wise):
         """Similarity head under autograd (VitaCLIP_model.py:248,255,287-293,308-309): 2*B*C*E flop on (B,E)/(C,E)
         tensors, traced by torch so that d logits reaches the text tower's backward and logit_scale."""
@@ -1247,10 +1274,14 @@ class VitaCLIP(nn.Module, _HipHost):
             elif self.use_text_prompt_learning:
                 self.text_features = tfeat            # VitaCLIP_model.py:293
 
-        # auxiliary heads: inactive at every accelerated configuration; kept as PyTorch glue on the device so that
+        # auxiliary heads: inactive at every accelerated configuration; by default PyTorch glue on the device so that
         # callers passing video_nte / memory still get the reference's outputs - and, in training, its gradients
-        # (`summary` and `text_features` carry the towers' autograd nodes).
-        if self.add_nte and video_nte is not None:              # VitaCLIP_model.py:311-345
+        # (`summary` and `text_features` carry the towers' autograd nodes); aux_heads = "hip" runs them as HIP kernels.
+        hip_aux = self.aux_heads == "hip"   # NteHeadFn / MemoryHeadFn: the same outputs and gradients from the kernels of aux_heads.hip
+        if hip_aux and self.add_nte and video_nte is not None:
+            from .training import NteHeadFn
+            logits_vm = NteHeadFn.apply(summary, self.sum_proj.weight, self.sum_proj.bias, video_nte, self.logit_scale_vm)
+        elif self.add_nte and video_nte is not None:            # VitaCLIP_model.py:311-345
             sp = self.sum_proj(summary)
             sp = sp / sp.norm(dim=-1, keepdim=True)
             with torch.no_grad():
@@ -1262,7 +1293,9 @@ class VitaCLIP(nn.Module, _HipHost):
             logits_vm = F.log_softmax(logits_mat, dim=-1) + F.log_softmax(logits_mat, dim=-2)
         else:
             logits_vm = None
-        if self.use_support_memory and memory is not None:      # VitaCLIP_model.py:347-398
+        if hip_aux and self.use_support_memory and memory is not None:
+            logits_mt = self._memory_head_hip(memory, self.text_features.detach() if self.detach_features else self.text_features)
+        elif self.use_support_memory and memory is not None:    # VitaCLIP_model.py:347-398
             text_features = self.text_features.detach() if self.detach_features else self.text_features
             memory = memory.mean(dim=1)
             logits_mt = torch.empty(memory.size(0), 0).to(memory.device)

@@ -488,8 +488,8 @@ class VisionTowerFn(torch.autograd.Function):
 # With VitaCLIP.train_head = "hip" the head between the towers' outputs and the logits is HeadFn (the inference head's kernels
 # forward, fp32 MFMA tiles backward) instead of the traced torch ops of VitaCLIP._train_head, and TrainCriterion is the
 # criterion of training/train.py:360-362,446-452 (cross-entropy x ordinal-focal weight of training/loss_utils.py:9-46, mean)
-# as two launches forward and one backward.  Not covered: soft (mixup) labels, the sigmoid memory criterion and the InfoNCE
-# variants of loss_utils.py - those stay torch code on the caller's side.
+# as two launches forward and one backward.  Not covered: soft (mixup) labels and the InfoNCE variants of loss_utils.py - those
+# stay torch code on the caller's side; the auxiliary heads and their terms (the sigmoid memory criterion among them) are further down.
 
 class HeadFn(torch.autograd.Function):
     """(logits [B, C], text_features [C, E]) = head(video [B, E], text [P, E], logit_scale, logit_bias or None, class_offsets):
@@ -566,3 +566,140 @@ class TrainCriterion:
         if self.track_confusion and (self.conf is None or self.conf.shape[0] != logits.shape[1] or self.conf.device != logits.device):
             self.conf = torch.zeros(logits.shape[1], logits.shape[1], dtype=torch.int32, device=logits.device)
         return _CriterionFn.apply(logits, labels.to(logits.device), self)
+
+
+# =================================================================================================
+# The auxiliary heads and their loss terms on the device (opt-in)
+# =================================================================================================
+# With VitaCLIP.aux_heads = "hip" the video<->NTE head and the support-memory<->text head (VitaCLIP_model.py:311-398) are
+# NteHeadFn and MemoryHeadFn - gava_nte_head* / gava_memory_head*, a constant number of launches whatever the batch and the
+# number of classes - instead of the traced torch ops of VitaCLIP._forward_impl, and AuxCriterion is loss_mt and loss_vm of
+# training/train.py:454-475.  Not covered: the InfoNCE / cosine-NCE variants of loss_utils.py (the reference's loop does not
+# call them) and soft targets.
+
+class NteHeadFn(torch.autograd.Function):
+    """logits_vm [B, B] = nte_head(summary [B, D], sum_proj.weight, sum_proj.bias, video_nte [B, K, E], logit_scale_vm).  Saved
+    for the backward: summary, the weight, the unit projected rows, the mean unit NTE rows and six [B] / [B, B] arrays - not
+    video_nte.  d summary goes back to the vision tower (VisionTowerFn's second output); a frozen parameter gets None."""
+    SAVED = ("summary", "weight", "logit_scale") + hip._NTE_KEPT
+
+    @staticmethod
+    def forward(fctx, summary, weight, bias, video_nte, logit_scale):
+        kept = hip.nte_head(summary, weight, bias, video_nte, logit_scale)
+        fctx.save_for_backward(*[kept[k] for k in NteHeadFn.SAVED])
+        fctx.dims = {k: kept[k] for k in ("B", "D", "E", "K")}
+        fctx.set_materialize_grads(False)
+        fctx.meta = [(t.shape, t.dtype) for t in (summary, weight, bias, logit_scale)]
+        return kept["logits_vm"]
+
+    @staticmethod
+    def backward(fctx, dlogits):
+        if dlogits is None:
+            return None, None, None, None, None
+        kept = dict(zip(NteHeadFn.SAVED, fctx.saved_tensors), **fctx.dims)
+        grads = hip.nte_head_backward(kept, dlogits)
+        need = [fctx.needs_input_grad[i] for i in (0, 1, 2, 4)]
+        out = [g.reshape(shape).to(dtype) if n else None for g, n, (shape, dtype) in zip(grads, need, fctx.meta)]
+        return out[0], out[1], out[2], None, out[3]
+
+
+class MemoryHeadFn(torch.autograd.Function):
+    """logits_mt [M, C] = memory_head(memory [M, S, E], text_features [C, E], logit_scale_mt, logit_bias_mt or None, the device
+    pointer table of memory_project's parameters, then tf_project's four parameters and memory_project's 4 C as inputs so that
+    autograd routes their gradients).  The per-class gradients are written into four stacked buffers and handed out as views.
+    d text_features is computed only when text_features asks for a gradient (detach_features passes a detached tensor)."""
+    SAVED = ("text_features", "tf_w1", "tf_b1", "tf_w2", "tf_b2", "mem_params", "logit_scale", "logit_bias") + hip._MEM_KEPT
+
+    @staticmethod
+    def forward(fctx, memory, text_features, logit_scale, logit_bias, mem_table, *params):
+        kept = hip.memory_head(memory, text_features, params[:4], mem_table, logit_scale, logit_bias)
+        fctx.save_for_backward(*[kept[k] for k in MemoryHeadFn.SAVED], *params[4:])      # (the table points into params[4:])
+        fctx.dims = {k: kept[k] for k in ("M", "S", "C", "E")}
+        fctx.set_materialize_grads(False)
+        fctx.meta = [(t.shape, t.dtype) if t is not None else None for t in (text_features, logit_scale, logit_bias)]
+        return kept["logits_mt"]
+
+    @staticmethod
+    def backward(fctx, dlogits):
+        n_par = len(fctx.needs_input_grad) - 5
+        if dlogits is None:
+            return (None,) * (5 + n_par)
+        kept = dict(zip(MemoryHeadFn.SAVED, fctx.saved_tensors), **fctx.dims)
+        need = fctx.needs_input_grad
+        g = hip.memory_head_backward(kept, dlogits, want_dtext=need[1])
+        cast = lambda t, meta: t.reshape(meta[0]).to(meta[1])
+        dtf = cast(g["dtext_features"], fctx.meta[0]) if need[1] else None
+        dls = cast(g["dlogit_scale"], fctx.meta[1]) if need[2] else None
+        dlb = cast(g["dlogit_bias"], fctx.meta[2]) if (fctx.meta[2] is not None and need[3]) else None
+        par = [g["dtf_w1"], g["dtf_b1"], g["dtf_w2"], g["dtf_b2"]]
+        for c in range(fctx.dims["C"]):
+            par += [g["dmem_w1"][c], g["dmem_b1"][c], g["dmem_w2"][c], g["dmem_b2"][c]]
+        return (None, dtf, dls, dlb, None, *[p if need[5 + i] else None for i, p in enumerate(par)])
+
+
+class _SigmoidCriterionFn(torch.autograd.Function):
+    @staticmethod
+    def forward(fctx, logits, labels, kw):
+        out = hip.sigmoid_criterion(logits.detach(), labels, **kw)
+        fctx.save_for_backward(logits.detach(), out["labels"])
+        fctx.kw = kw
+        return out["loss"]
+
+    @staticmethod
+    def backward(fctx, g):
+        logits, labels = fctx.saved_tensors
+        return hip.sigmoid_criterion_backward(logits, labels, g.float().contiguous(), **fctx.kw), None, None
+
+
+class _NteDiagFn(torch.autograd.Function):
+    @staticmethod
+    def forward(fctx, logits_vm, weight):
+        fctx.B, fctx.weight = logits_vm.shape[0], weight
+        return hip.nte_diag_loss(logits_vm.detach(), weight)
+
+    @staticmethod
+    def backward(fctx, g):
+        return hip.nte_diag_loss_backward(fctx.B, g.float().contiguous(), fctx.weight), None
+
+
+class AuxCriterion:
+    """(loss_mt, loss_vm) = crit(logits_mt=None, mt_labels=None, logits_vm=None): the auxiliary loss terms of the reference's
+    training loop (training/train.py:454-475) on the device, as scalars under autograd; a term whose logits are None is None.
+
+    loss_mt, sigmoid=False: memory_loss_weight * mean cross-entropy(logits_mt, mt_labels), through gava_train_criterion
+    (unweighted).  sigmoid=True: memory_loss_weight * mean(sigmoid_focal_loss(scale=memory_loss_weight)(logits_mt, mt_labels))
+    through gava_sigmoid_criterion - the weight enters TWICE, as it does in the reference, which builds the criterion with
+    scale=args.memory_loss_weight (train.py:365) and multiplies its result by args.memory_loss_weight again (train.py:459).
+    use_focal / alpha / gamma are sigmoid_focal_loss's (loss_utils.py:139-177; the reference's loop passes use_focal=False).
+    loss_vm = -vnte_loss_weight * mean of the diagonal of logits_vm (gava_nte_diag_loss).
+    Integer labels [M] only: soft targets are refused."""
+
+    def __init__(self, memory_loss_weight=1.0, vnte_loss_weight=1.0, sigmoid=False, alpha=0.25, gamma=2.0, use_focal=False):
+        if use_focal and not gamma >= 1.0:
+            raise hip.GavaError("AuxCriterion needs gamma >= 1 with use_focal: the focal factor's derivative is unbounded at p = 1 below that")
+        self.memory_loss_weight, self.vnte_loss_weight = float(memory_loss_weight), float(vnte_loss_weight)
+        self.sigmoid, self.alpha, self.gamma, self.use_focal = bool(sigmoid), float(alpha), float(gamma), bool(use_focal)
+        self._ce = TrainCriterion()
+
+    @staticmethod
+    def _logits(t, what):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dim() == 2):
+            raise hip.GavaError(f"AuxCriterion takes device {what} of two dimensions")
+        return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
+
+    def __call__(self, logits_mt=None, mt_labels=None, logits_vm=None):
+        loss_mt = loss_vm = None
+        if logits_mt is not None:
+            if not (torch.is_tensor(mt_labels) and not mt_labels.is_floating_point() and mt_labels.dim() == 1):
+                raise hip.GavaError("AuxCriterion takes integer class labels [M]; soft targets are not supported")
+            logits_mt = self._logits(logits_mt, "logits_mt")
+            if self.sigmoid:
+                kw = dict(use_focal=self.use_focal, alpha=self.alpha, gamma=self.gamma, scale=self.memory_loss_weight ** 2)
+                loss_mt = _SigmoidCriterionFn.apply(logits_mt, mt_labels, kw)
+            else:
+                loss_mt = self._ce(logits_mt, mt_labels)
+                if self.memory_loss_weight != 1.0:
+                    loss_mt = loss_mt * self.memory_loss_weight
+        if logits_vm is not None:
+            loss_vm = _NteDiagFn.apply(self._logits(logits_vm, "logits_vm"), self.vnte_loss_weight)
+        return loss_mt, loss_vm

@@ -619,6 +619,101 @@ int gava_train_head_backward(const gava_train_head_args* a, gava_stream_t stream
  * compares that call's return value with its own count).  Writes min(cap, 2) entries, returns 2. */
 int gava_train_struct_sizes(size_t* out, int cap);
 
+/* ---- auxiliary heads and their loss terms (opt-in: VitaCLIP.aux_heads = "hip", gava_clip_amd.AuxCriterion) ------------------
+ *
+ * All fp32, no atomics (the same bits on every run), no host synchronisation; upstream gradients are read from device memory.
+ * The number of launches of an entry point does not depend on B, M, C or S.  Pointers that rows are read from 16 bytes at a
+ * time (summary, weight, video_nte, memory, text_features, the weights, the kept buffers) must be 16-byte aligned.
+ *
+ * Video <-> NTE head (VitaCLIP_model.py:311-345).  summary [B][D], weight [E][D] and bias [E] of sum_proj (bias optional),
+ * video_nte [B][K][E], logit_scale one float (multiplied as it is, no exp).
+ *   sp = unit rows of summary weight^T + bias;  n[j] = mean over k of the unit rows of video_nte[j];  valid[j] = (the sum of
+ *   all elements of video_nte[j] != 0);  sim = sp n^T valid_i valid_j  (the mean of the K products of the reference, by
+ *   linearity);  lm = logit_scale * sim;  logits_vm = log_softmax(lm, rows) + log_softmax(lm, columns)
+ * The forward keeps sp_norm [B][E], sp_inv [B] (1 / |row|), nte_mean [B][E], valid [B] (0 / 1), sim [B][B] (masked), lm [B][B],
+ * row_lse [B], col_lse [B].  The backward takes dlogits [B][B] and what was kept (video_nte and logits_vm may be NULL there):
+ *   dlm = 2 g - exp(lm - row_lse_i) sum_j g_ij - exp(lm - col_lse_j) sum_i g_ij;   dlogit_scale = sum dlm sim
+ *   dsp = (dlm logit_scale valid_i valid_j) n;   dy = (dsp - sp <sp, dsp>) sp_inv;   dweight = dy^T summary, dbias = sum_b dy,
+ *   dsummary = dy weight
+ * workspace: B * (B + E + 3) floats.  D % 4 == 0, E % 4 == 0, E <= 1024, B <= 32767.  A video_nte row of norm zero gives
+ * unspecified (NaN) outputs, as in the reference; every index stays in range.  Five launches forward, five backward. */
+typedef struct {
+  const float* summary; const float* weight; const float* bias; const float* video_nte; const float* logit_scale;
+  int B, D, E, K;
+  float* logits_vm;
+  float* sp_norm; float* sp_inv; float* nte_mean; float* valid; float* sim; float* lm; float* row_lse; float* col_lse;
+  const float* dlogits;                                      /* backward only from here */
+  float* dsummary; float* dweight; float* dbias; float* dlogit_scale;
+  float* workspace;
+} gava_nte_head_args;
+int gava_nte_head(const gava_nte_head_args* a, gava_stream_t stream);
+int gava_nte_head_backward(const gava_nte_head_args* a, gava_stream_t stream);
+
+/* Support-memory <-> text head (VitaCLIP_model.py:347-398).  memory [M][S][E], text_features [C][E]; an MLP is Linear E -> H1 =
+ * E / 4, tanh, Linear H1 -> H2 = E / 8.  tf_project's four parameters are passed directly (tf_w1 [H1][E], tf_b1 [H1], tf_w2
+ * [H2][H1], tf_b2 [H2]); memory_project[c]'s through mem_params, a DEVICE table of C x 4 pointers in that order (built once
+ * by the caller: nothing is launched or copied per class).  logit_scale one float (no exp), logit_bias optional.
+ *   mm = mean_s memory;  z_c = memory_project[c](mm) [M][H2];  u_c = tf_project(text_features[c]) [H2]
+ *   cos[m][c] = <z_c[m], u_c> / (|z_c[m]| |u_c|);   logits_mt = log_softmax(logit_scale * cos, classes) + logit_bias
+ * The forward keeps mem_mean [M][E], mem_h [C][M][H1] (tanh outputs), mem_z [C][M][H2], mem_inv [M][C] (1 / |z_c[m]|), tf_h
+ * [C][H1], tf_u [C][H2], tf_inv [C], cosine [M][C], lse [M].  The backward takes dlogits [M][C] and what was kept (memory and
+ * logits_mt may be NULL there) and writes the stacked gradients dmem_w1 [C][H1][E], dmem_b1 [C][H1], dmem_w2 [C][H2][H1],
+ * dmem_b2 [C][H2], tf_project's dtf_* (summed over the classes in class order), dlogit_scale, dlogit_bias (required when
+ * logit_bias is given) and dtext_features [C][E] (optional: NULL = not computed):
+ *   draw = g - softmax sum_c g;  dlogit_scale = sum draw cos;  dlogit_bias = sum g;  dcos = draw logit_scale
+ *   dz_c[m] = dcos (u^ - z^ cos) / |z|;   du_c = (d - u^ <u^, d>) / |u|,  d = sum_m dcos[m][c] z^_c[m];   then each MLP's backward
+ * workspace: gava_memory_head_backward_workspace_floats.  E % 16 == 0, C <= 65535.  Six launches forward, ten backward (nine
+ * without dtext_features). */
+typedef struct {
+  const float* memory; const float* text_features;
+  const float* tf_w1; const float* tf_b1; const float* tf_w2; const float* tf_b2;
+  const float* const* mem_params;
+  const float* logit_scale; const float* logit_bias;
+  int M, S, C, E;
+  float* logits_mt;
+  float* mem_mean; float* mem_h; float* mem_z; float* mem_inv; float* tf_h; float* tf_u; float* tf_inv; float* cosine; float* lse;
+  const float* dlogits;                                      /* backward only from here */
+  float* dmem_w1; float* dmem_b1; float* dmem_w2; float* dmem_b2;
+  float* dtf_w1; float* dtf_b1; float* dtf_w2; float* dtf_b2;
+  float* dlogit_scale; float* dlogit_bias; float* dtext_features;
+  float* workspace;
+} gava_memory_head_args;
+int gava_memory_head(const gava_memory_head_args* a, gava_stream_t stream);
+int gava_memory_head_backward(const gava_memory_head_args* a, gava_stream_t stream);
+size_t gava_memory_head_backward_workspace_floats(int M, int C, int E);
+size_t gava_nte_head_backward_workspace_floats(int B, int E);
+
+/* sigmoid_focal_loss of training/loss_utils.py:139-177 on integer labels, then the mean over the samples.  With t = +1 at the
+ * label and -1 elsewhere, ce = softplus(-t x) (= -logsigmoid(t x), written so that large |x| loses no accuracy) and
+ * q = sigmoid(-t x) = 1 - p_t:
+ *   per_sample[m] = scale * sum_c (use_focal ? alpha_t q^gamma ce : ce),  alpha_t = alpha at the label, 1 - alpha elsewhere
+ *   loss = mean_m per_sample;   dlogits = grad_loss / M * scale * -t (use_focal ? alpha_t q^gamma (gamma (1 - q) ce + q) : q)
+ * A label outside [0, C) marks no class.  GAVA_EINVAL: use_focal with gamma < 1, M < 1, C < 1, a null pointer among the required
+ * ones.  Two launches forward (rows, mean), one backward. */
+typedef struct {
+  const float* logits; int64_t ld_logits;     /* fp32 [M][C], rows ld_logits elements apart */
+  const int64_t* labels;                      /* [M] */
+  int M, C, use_focal;
+  float alpha, gamma, scale;
+  float* loss; float* per_sample;
+  const float* grad_loss; float* dlogits; int64_t ld_dlogits;     /* backward only */
+} gava_sigmoid_criterion_args;
+int gava_sigmoid_criterion(const gava_sigmoid_criterion_args* a, gava_stream_t stream);
+int gava_sigmoid_criterion_backward(const gava_sigmoid_criterion_args* a, gava_stream_t stream);
+
+/* loss = -weight * mean_i logits_vm[i][i] (training/train.py:471-475), logits_vm [B][B] contiguous; the backward writes the
+ * whole dlogits_vm [B][B] (-weight * grad_loss / B on the diagonal, zero elsewhere).  One launch each. */
+typedef struct {
+  const float* logits_vm; int B; float weight;
+  float* loss;
+  const float* grad_loss; float* dlogits_vm;                      /* backward only */
+} gava_nte_diag_args;
+int gava_nte_diag_loss(const gava_nte_diag_args* a, gava_stream_t stream);
+int gava_nte_diag_loss_backward(const gava_nte_diag_args* a, gava_stream_t stream);
+
+/* sizeof of the four structs above, in that order, like gava_train_struct_sizes.  Writes min(cap, 4) entries, returns 4. */
+int gava_aux_struct_sizes(size_t* out, int cap);
+
 /* sizeof of every ABI struct as the library was compiled, in the order gemm_args, layernorm_args, attention_args,
  * attention_f32_args, clip_desc, vision_layer, vision_layer8, vision_model, text_layer, text_model, layernorm_bwd_args,
  * attention_bwd_args, vision_saved, preprocess_args, patchify_args, preprocess_clips_args, view_scores_args.  Writes
