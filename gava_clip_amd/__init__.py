@@ -16,4 +16,7 @@ def __getattr__(name):  # lazy: importing the package must not need torch/HIP
     if name == "AuxCriterion":
         from .training import AuxCriterion
         return AuxCriterion
+    if name == "FusedAdamW":
+        from .optim import FusedAdamW
+        return FusedAdamW
     raise AttributeError(name)

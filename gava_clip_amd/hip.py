@@ -31,7 +31,9 @@ EXPORTS = ["gava_abi_version", "gava_gemm", "gava_layernorm", "gava_attention",
            "gava_nte_head", "gava_nte_head_backward", "gava_memory_head", "gava_memory_head_backward",
            "gava_memory_head_backward_workspace_floats", "gava_nte_head_backward_workspace_floats",
            "gava_sigmoid_criterion", "gava_sigmoid_criterion_backward", "gava_nte_diag_loss", "gava_nte_diag_loss_backward",
-           "gava_aux_struct_sizes"]
+           "gava_aux_struct_sizes",
+           "gava_adamw_plan", "gava_adamw_step", "gava_optim_struct_sizes"]
+ADAMW_MAX_GROUPS = 8
 
 _vp, _fp, _ip = C.c_void_p, C.c_void_p, C.c_void_p  # all device pointers travel as void*
 
@@ -189,6 +191,27 @@ class NteDiagArgs(C.Structure):
     _fields_ = [("logits_vm", _fp), ("B", C.c_int), ("weight", C.c_float), ("loss", _fp), ("grad_loss", _fp), ("dlogits_vm", _fp)]
 
 
+class AdamWTensor(C.Structure):
+    _fields_ = [("p", _fp), ("g", _fp), ("m", _fp), ("v", _fp), ("step", _fp),
+                ("copy_f32", _fp), ("copy16", _vp), ("copy_bf16", _vp), ("copy_bf16_t", _vp),
+                ("ld_f32", C.c_int64), ("ld16", C.c_int64), ("ld_bf16", C.c_int64), ("ld_bf16_t", C.c_int64),
+                ("n", C.c_int), ("group", C.c_int), ("rows", C.c_int), ("cols", C.c_int), ("prec16", C.c_int), ("reserved", C.c_int)]
+
+
+class AdamWChunk(C.Structure):
+    _fields_ = [("tensor", C.c_int), ("a", C.c_int), ("b", C.c_int), ("reserved", C.c_int)]
+
+
+class AdamWGroup(C.Structure):
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double)]
+
+
+class AdamWArgs(C.Structure):
+    _fields_ = [("table", _vp), ("table_host", C.POINTER(AdamWTensor)), ("chunks", _vp),
+                ("n_tensors", C.c_int), ("n_chunks", C.c_int), ("n_groups", C.c_int), ("reserved", C.c_int),
+                ("groups", AdamWGroup * 8), ("grad_scale", _fp), ("found_inf", _fp)]
+
+
 class PatchifyArgs(C.Structure):
     _fields_ = [("x", _fp), ("clips", _vp), ("clip_lut", _fp),
                 ("B", C.c_int), ("T", C.c_int), ("size", C.c_int), ("patch", C.c_int), ("prec", C.c_int),
@@ -344,6 +367,18 @@ def load():
     if lib.gava_aux_struct_sizes(sizes, len(aux_mirrors)) != len(aux_mirrors):
         raise GavaError("libgava_hip.so and gava_clip_amd/hip.py disagree on the number of auxiliary-head ABI structs")
     for cls, sz in zip(aux_mirrors, sizes):
+        if C.sizeof(cls) != sz:
+            raise GavaError(f"ctypes mirror {cls.__name__} is {C.sizeof(cls)} bytes, the library's struct {sz}: gava_clip_amd/hip.py is out of "
+                            f"step with include/gava_hip.h")
+    # the fused optimizer's structs, the same way
+    optim_mirrors = [AdamWTensor, AdamWArgs, AdamWChunk]
+    lib.gava_adamw_plan.argtypes = [C.POINTER(AdamWTensor), C.c_int, C.c_int, C.POINTER(AdamWChunk), C.c_int]
+    lib.gava_adamw_plan.restype = C.c_int
+    lib.gava_adamw_step.argtypes, lib.gava_adamw_step.restype = [C.POINTER(AdamWArgs), _vp], C.c_int
+    lib.gava_optim_struct_sizes.argtypes, lib.gava_optim_struct_sizes.restype = [C.POINTER(C.c_size_t), C.c_int], C.c_int
+    if lib.gava_optim_struct_sizes(sizes, len(optim_mirrors)) != len(optim_mirrors):
+        raise GavaError("libgava_hip.so and gava_clip_amd/hip.py disagree on the number of optimizer ABI structs")
+    for cls, sz in zip(optim_mirrors, sizes):
         if C.sizeof(cls) != sz:
             raise GavaError(f"ctypes mirror {cls.__name__} is {C.sizeof(cls)} bytes, the library's struct {sz}: gava_clip_amd/hip.py is out of "
                             f"step with include/gava_hip.h")

@@ -714,6 +714,65 @@ int gava_nte_diag_loss_backward(const gava_nte_diag_args* a, gava_stream_t strea
 /* sizeof of the four structs above, in that order, like gava_train_struct_sizes.  Writes min(cap, 4) entries, returns 4. */
 int gava_aux_struct_sizes(size_t* out, int cap);
 
+/* ---- fused AdamW step (opt-in: gava_clip_amd.FusedAdamW) ---------------------------------------------------------------------
+ *
+ * Multi-tensor AdamW (torch.optim.AdamW with amsgrad = False, maximize = False) over a DEVICE-resident table of tensor
+ * descriptors, in two launches however many tensors the table holds (the update over a chunk list, then the step counts),
+ * with no allocation and no host synchronisation.  Per element, in fp32, with t = *step + 1 read from the device:
+ *   g <- g * (1 / *grad_scale);  p <- p * (1 - lr * wd);  m <- m + (g - m) * (1 - beta1);  v <- beta2 * v + (1 - beta2) * g * g
+ *   p <- p - (lr / (1 - beta1^t)) * (m / (sqrt(v) / sqrt(1 - beta2^t) + eps))
+ * 1 - lr * wd and the two bias corrections are evaluated in double, once per workgroup.  g is read only: the unscaled gradient is not
+ * written back.  If *found_inf != 0 the call changes nothing (not p, m, v, the step counts or any copy); otherwise every step
+ * count of a tensor with a gradient goes up by one in the trailing launch, after every chunk has computed from the old one.
+ *
+ * A table entry describes one parameter.  g == NULL skips it entirely (no decay, no step increment, no copy: torch's behaviour
+ * for p.grad is None).  Besides the update the kernel writes up to four copies of the UPDATED parameter from the values it
+ * holds in registers, the parameter seen as a rows x cols matrix (rows * cols == n; NULL = no such copy):
+ *   copy_f32     fp32,                      copy_f32[r * ld_f32 + c]
+ *   copy16       prec16 (GAVA_PREC_*),      copy16[r * ld16 + c]
+ *   copy_bf16    bf16,                      copy_bf16[r * ld_bf16 + c]
+ *   copy_bf16_t  bf16, the transpose,       copy_bf16_t[c * ld_bf16_t + r]      (through an LDS tile: both sides coalesced)
+ * with explicit leading dimensions (in elements), so that separate q, k and v parameters land in the row blocks of one
+ * [3D][D] copy and in the column blocks of one [D][3D] transposed copy.  The 16-bit values are the bits gava_convert_h16
+ * gives for the updated parameter.  16-byte loads and stores are used wherever the addresses allow, element-wise ones elsewhere:
+ * no alignment is required beyond the element's own.
+ *
+ * The chunk list (DEVICE, one workgroup per entry) is written by gava_adamw_plan from the HOST copy of the table: at most 4096
+ * elements of one tensor per chunk, as a linear range or, for a tensor with a transposed copy, a 64 x 64 tile.  Tensors
+ * without a gradient get no chunk.  gava_adamw_plan writes min(cap, count) entries and returns count (call it with cap = 0 to
+ * size the buffer), or GAVA_EINVAL.
+ *
+ * gava_adamw_step reads table_host (the same descriptors in host memory; it is not kept) to validate before any launch.
+ * GAVA_EINVAL: null args, a null table or table_host with n_tensors > 0, null chunks with n_chunks > 0, n_groups outside
+ * [1, GAVA_ADAMW_MAX_GROUPS], and per tensor with a gradient: a null p, m, v or step, n < 0, a group index outside [0, n_groups),
+ * with a 16-bit copy16 a prec16 outside {GAVA_PREC_F16, GAVA_PREC_BF16}, with any copy target rows * cols != n or a leading
+ * dimension smaller than the row it holds.  The hyper-parameters travel BY VALUE: a schedule that changes lr every step
+ * uploads nothing. */
+#define GAVA_ADAMW_MAX_GROUPS 8
+typedef struct {
+  float* p; const float* g; float* m; float* v;     /* fp32, n elements each, contiguous */
+  float* step;                                      /* this tensor's step count, one fp32 */
+  float* copy_f32; void* copy16; void* copy_bf16; void* copy_bf16_t;
+  int64_t ld_f32, ld16, ld_bf16, ld_bf16_t;
+  int n, group, rows, cols, prec16, reserved;
+} gava_adamw_tensor;
+typedef struct { int tensor, a, b, reserved; } gava_adamw_chunk;   /* linear: elements [a, a + b); tile: rows from a, columns from b */
+typedef struct { double lr, beta1, beta2, eps, weight_decay; } gava_adamw_group;
+typedef struct {
+  const gava_adamw_tensor* table;        /* DEVICE, n_tensors entries */
+  const gava_adamw_tensor* table_host;   /* the same entries in host memory (validation only) */
+  const gava_adamw_chunk* chunks;        /* DEVICE, n_chunks entries (gava_adamw_plan) */
+  int n_tensors, n_chunks, n_groups, reserved;
+  gava_adamw_group groups[GAVA_ADAMW_MAX_GROUPS];
+  const float* grad_scale; const float* found_inf;   /* device scalars, either may be NULL */
+} gava_adamw_args;
+int gava_adamw_plan(const gava_adamw_tensor* table_host, int n_tensors, int n_groups, gava_adamw_chunk* out, int cap);
+int gava_adamw_step(const gava_adamw_args* a, gava_stream_t stream);
+
+/* sizeof of gava_adamw_tensor, gava_adamw_args, gava_adamw_chunk, in that order, like gava_aux_struct_sizes.  Writes
+ * min(cap, 3) entries, returns 3. */
+int gava_optim_struct_sizes(size_t* out, int cap);
+
 /* sizeof of every ABI struct as the library was compiled, in the order gemm_args, layernorm_args, attention_args,
  * attention_f32_args, clip_desc, vision_layer, vision_layer8, vision_model, text_layer, text_model, layernorm_bwd_args,
  * attention_bwd_args, vision_saved, preprocess_args, patchify_args, preprocess_clips_args, view_scores_args.  Writes
