@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("GAVA_HIP_LIB") or os.path.join(_HERE, "libgava_hip.so
 PREC_F16, PREC_BF16 = 0, 1
 KERNEL_AUTO, KERNEL_256, KERNEL_PAIR, KERNEL_PP = 0, 3, 4, 5     # gava_gemm_args.kernel
 EPI_H16, EPI_H16_QGELU, EPI_F32, EPI_F32_PATCH, EPI_H16_QGELU_BWD = 0, 1, 2, 3, 4
+UNPATCH_GRAD, UNPATCH_ABSMAX, UNPATCH_L2, UNPATCH_GRAD_X_INPUT = 0, 1, 2, 3      # gava_unpatchify_args.mode
 MAX_GRID_FRAMES = 65535      # clips x frames one gava_preprocess_clips / gava_patchify launch covers (its grid's z extent)
 PREC_NAMES = {"fp16": PREC_F16, "f16": PREC_F16, "bf16": PREC_BF16}
 PREC_TORCH = {PREC_F16: torch.float16, PREC_BF16: torch.bfloat16}
@@ -32,7 +33,8 @@ EXPORTS = ["gava_abi_version", "gava_gemm", "gava_layernorm", "gava_attention",
            "gava_memory_head_backward_workspace_floats", "gava_nte_head_backward_workspace_floats",
            "gava_sigmoid_criterion", "gava_sigmoid_criterion_backward", "gava_nte_diag_loss", "gava_nte_diag_loss_backward",
            "gava_aux_struct_sizes",
-           "gava_adamw_plan", "gava_adamw_step", "gava_optim_struct_sizes"]
+           "gava_adamw_plan", "gava_adamw_step", "gava_optim_struct_sizes",
+           "gava_unpatchify", "gava_input_grad_struct_sizes"]
 ADAMW_MAX_GROUPS = 8
 
 _vp, _fp, _ip = C.c_void_p, C.c_void_p, C.c_void_p  # all device pointers travel as void*
@@ -218,6 +220,12 @@ class PatchifyArgs(C.Structure):
                 ("out", _vp), ("ldo", C.c_int64)]
 
 
+class UnpatchifyArgs(C.Structure):
+    _fields_ = [("dpatch", _fp), ("ld", C.c_int64), ("x", _fp), ("out", _fp),
+                ("B", C.c_int), ("T", C.c_int), ("size", C.c_int), ("patch", C.c_int), ("mode", C.c_int),
+                ("frame_rows", C.c_int), ("row_offset", C.c_int), ("reserved", C.c_int)]
+
+
 class VisionSaved(C.Structure):
     _fields_ = [("e0", _fp), ("x", _fp), ("x1", _fp), ("qkv", _vp), ("pre", _vp), ("sidekv", _vp),
                 ("last_q", _vp), ("last_x1", _fp), ("last_pre", _vp)]
@@ -379,6 +387,16 @@ def load():
     if lib.gava_optim_struct_sizes(sizes, len(optim_mirrors)) != len(optim_mirrors):
         raise GavaError("libgava_hip.so and gava_clip_amd/hip.py disagree on the number of optimizer ABI structs")
     for cls, sz in zip(optim_mirrors, sizes):
+        if C.sizeof(cls) != sz:
+            raise GavaError(f"ctypes mirror {cls.__name__} is {C.sizeof(cls)} bytes, the library's struct {sz}: gava_clip_amd/hip.py is out of "
+                            f"step with include/gava_hip.h")
+    # the input gradient's struct, the same way
+    input_grad_mirrors = [UnpatchifyArgs]
+    lib.gava_unpatchify.argtypes, lib.gava_unpatchify.restype = [C.POINTER(UnpatchifyArgs), _vp], C.c_int
+    lib.gava_input_grad_struct_sizes.argtypes, lib.gava_input_grad_struct_sizes.restype = [C.POINTER(C.c_size_t), C.c_int], C.c_int
+    if lib.gava_input_grad_struct_sizes(sizes, len(input_grad_mirrors)) != len(input_grad_mirrors):
+        raise GavaError("libgava_hip.so and gava_clip_amd/hip.py disagree on the number of input-gradient ABI structs")
+    for cls, sz in zip(input_grad_mirrors, sizes):
         if C.sizeof(cls) != sz:
             raise GavaError(f"ctypes mirror {cls.__name__} is {C.sizeof(cls)} bytes, the library's struct {sz}: gava_clip_amd/hip.py is out of "
                             f"step with include/gava_hip.h")
@@ -559,6 +577,38 @@ def patchify(out, *, B, T, size, patch, prec, x=None, clips=None, clip_lut=None)
     a.B, a.T, a.size, a.patch, a.prec = B, T, size, patch, prec
     a.out, a.ldo = ptr(out), out.stride(0)
     check(load().gava_patchify(C.byref(a), stream_ptr()), "gava_patchify")
+
+
+def unpatchify(dpatch, out, *, B, T, size, patch, mode, frame_rows, row_offset, x=None):
+    """The fold half of the patch embedding (gava_unpatchify, the inverse of patchify's index map): dpatch fp32
+    [B*T*frame_rows, ld] (or [B*T, frame_rows, ld]), of which rows row_offset ... row_offset + (size/patch)^2 - 1 of every
+    frame and columns [0, 3*patch^2) are read -> out fp32 [B, 3, T, size, size] (mode UNPATCH_GRAD) or the map [B, T, size,
+    size] of UNPATCH_ABSMAX / UNPATCH_L2 / UNPATCH_GRAD_X_INPUT; the last one takes the fp32 clip x [B, 3, T, size, size]."""
+    _require(mode in (UNPATCH_GRAD, UNPATCH_ABSMAX, UNPATCH_L2, UNPATCH_GRAD_X_INPUT), f"unpatchify: unknown mode {mode!r}")
+    _require((mode == UNPATCH_GRAD_X_INPUT) == (x is not None), "unpatchify: x goes with mode UNPATCH_GRAD_X_INPUT and with no other")
+    for name, t in (("dpatch", dpatch), ("out", out), ("x", x)):
+        _require(t is None or (torch.is_tensor(t) and t.dtype == torch.float32 and t.is_contiguous()),
+                 f"unpatchify: {name} must be a contiguous fp32 tensor")
+    _require(min(B, T, size, patch) > 0 and size % patch == 0, f"unpatchify: B={B} T={T} size={size} patch={patch}")
+    n = (size // patch) ** 2
+    _require(dpatch.dim() in (2, 3) and dpatch.numel() == B * T * frame_rows * dpatch.shape[-1] and
+             (dpatch.dim() == 2 or dpatch.shape[1] == frame_rows),
+             f"unpatchify: dpatch {tuple(dpatch.shape)} is not {B * T} frames of {frame_rows} rows")
+    _require(dpatch.shape[-1] >= 3 * patch * patch, f"unpatchify: rows of {dpatch.shape[-1]} floats hold no {3 * patch * patch} patch columns")
+    _require(0 <= row_offset and row_offset + n <= frame_rows, f"unpatchify: rows {row_offset} ... {row_offset + n - 1} of a frame of {frame_rows}")
+    clip = (B, 3, T, size, size)
+    want = clip if mode == UNPATCH_GRAD else (B, T, size, size)
+    _require(tuple(out.shape) == want, f"unpatchify: out is {tuple(out.shape)}, this mode writes {want}")
+    _require(x is None or tuple(x.shape) == clip, f"unpatchify: x is {tuple(x.shape) if x is not None else None}, not {clip}")
+    for name, t in (("dpatch", dpatch), ("out", out), ("x", x)):
+        _require(t is None or t.is_cuda, f"unpatchify: {name} must be on the HIP device: there is no CPU fallback")
+    _require(dpatch.device == out.device and (x is None or x.device == out.device), "unpatchify: tensors on different devices")
+    a = UnpatchifyArgs()
+    a.dpatch, a.ld, a.x, a.out = ptr(dpatch), dpatch.shape[-1], ptr(x), ptr(out)
+    a.B, a.T, a.size, a.patch, a.mode, a.frame_rows, a.row_offset = B, T, size, patch, mode, frame_rows, row_offset
+    with torch.cuda.device(out.device):
+        check(load().gava_unpatchify(C.byref(a), stream_ptr(out.device)), "gava_unpatchify")
+    return out
 
 
 # ---- backward ops (SURVEY 8f row 1) ------------------------------------------------------------

@@ -1162,7 +1162,57 @@ class VitaCLIP(nn.Module, _HipHost):
             self.cache_text_features = cached
         return scores, logits, top1
 
-    def _forward_impl(self, x, memory, video_nte, desc_wise, clips=None):
+    _SALIENCY_MODES = {None: hip.UNPATCH_GRAD, "absmax": hip.UNPATCH_ABSMAX, "l2": hip.UNPATCH_L2, "grad_x_input": hip.UNPATCH_GRAD_X_INPUT}
+
+    def saliency(self, x, target=None, reduce="absmax"):
+        """Which pixels and frames of the clips moved a class score: the gradient of sum_b logits[b, target_b] (the raw
+        logits) with respect to x, through the HIP backward of the frozen vision tower.
+        -> (maps, logits [B, C], target int64 [B]); maps is fp32 [B, T, S, S], per pixel over the three channels
+             reduce="absmax"        max_c |g_c|
+             reduce="l2"            sqrt(sum_c g_c^2)
+             reduce="grad_x_input"  sum_c g_c x_c
+        or, with reduce=None, the gradient itself, fp32 [B, 3, T, S, S] - the bits x.grad gets from forward(x) followed by
+        the same backward.  The map modes fold the patch gradients straight into the map (gava_unpatchify): the full-size
+        gradient is never in memory.
+        x: a device clip batch [B, 3, T, S, S] as forward() takes it; it need not require grad (decoded uint8 videos:
+        preprocess with `preprocessor.batch(videos)` first).  target: None - the top-1 class of this very forward, picked on the
+        device -, an int (checked against the number of classes on the host), or an int64 [B] device tensor, which is NOT
+        range-checked (a check would wait for the device; an index outside [0, C) is a device-side fault).
+        Works on a model in eval() or train() mode, whatever is trainable; no parameter's .grad is touched, no graph and no
+        kept activation survives the call, and the call itself never waits for the device.  memory / video_nte / desc_wise
+        have no part in it; a ragged (use_descriptor) head is refused.  With an initialised process group every rank works
+        on its own clips, as every grad-enabled forward does."""
+        if reduce not in self._SALIENCY_MODES:
+            raise hip.GavaError(f"saliency: reduce must be one of 'absmax', 'l2', 'grad_x_input' or None, got {reduce!r}")
+        if not (torch.is_tensor(x) and x.is_cuda):
+            raise hip.GavaError("VitaCLIP (gava_clip_amd) runs on the HIP device only: move the model and the "
+                                "input with .cuda(); there is no CPU fallback")
+        if not (x.dim() == 5 and x.is_floating_point()):
+            raise hip.GavaError(f"saliency takes a floating-point clip batch [B, 3, T, S, S], got {x.dtype} {tuple(x.shape)}")
+        if self.use_text_prompt_learning and self.prompt_learner.n_kv is None:
+            raise hip.GavaError("saliency: a per-descriptor (use_descriptor / desc_wise) head has no single logit per class to differentiate")
+        n_cls = self.prompt_learner.n_cls if self.use_text_prompt_learning else self.text_features.shape[0]
+        if target is not None and not torch.is_tensor(target):
+            if not 0 <= int(target) < n_cls:
+                raise hip.GavaError(f"saliency: target {target} is outside the {n_cls} classes")
+        elif target is not None and not (target.is_cuda and target.dtype == torch.int64 and tuple(target.shape) == (x.shape[0],)):
+            raise hip.GavaError(f"saliency: a tensor target must be int64 [{x.shape[0]}] on the device")
+        mode = self._SALIENCY_MODES[reduce]
+        with torch.cuda.device(x.device), torch.enable_grad():
+            xg = x.detach().float().contiguous().requires_grad_()       # a leaf of this call's own: x is left alone
+            request = dict(mode=mode, x=xg.detach() if mode == hip.UNPATCH_GRAD_X_INPUT else None)
+            logits = self._forward_impl(xg, None, None, False, input_request=request)[0]
+            if target is None:
+                target = logits.detach().argmax(dim=1)
+            elif not torch.is_tensor(target):
+                target = torch.full((x.shape[0],), int(target), dtype=torch.int64, device=x.device)
+            score = logits.gather(1, target.view(-1, 1)).sum()
+            (dx,) = torch.autograd.grad(score, [xg], allow_unused=True)      # runs the vision tower's backward, nothing else
+        if torch.is_tensor(self.text_features) and self.text_features.requires_grad:
+            self.text_features = self.text_features.detach()        # the last reference into this call's graph
+        return (dx if mode == hip.UNPATCH_GRAD else request.pop("out")), logits.detach(), target
+
+    def _forward_impl(self, x, memory, video_nte, desc_wise, clips=None, input_request=None):
         lib = hip.load()
         if clips is not None:
             B, T = clips[1], clips[2]
@@ -1173,6 +1223,10 @@ class VitaCLIP(nn.Module, _HipHost):
         if not x.is_cuda:
             raise hip.GavaError("VitaCLIP (gava_clip_amd) runs on the HIP device only: move the model and the "
                                 "input with .cuda(); there is no CPU fallback")
+        want_dx = clips is None and torch.is_grad_enabled() and x.requires_grad
+        if want_dx and x.dtype != torch.float32:
+            raise hip.GavaError(f"the gradient with respect to the input clip is computed for fp32 clips only, x is {x.dtype}: "
+                                "pass x.float(), or detach x")
         text, text_stream = None, None
         self._attach_encoders()
         self._pack()   # (re)pack weights on the caller's stream, before any fork
@@ -1219,11 +1273,12 @@ class VitaCLIP(nn.Module, _HipHost):
                 self._text_cache = (key, text) if key is not None else None
         else:
             text = self.text_features.to(device=x.device, dtype=torch.float32).contiguous()
-        train_vision = torch.is_grad_enabled() and any(p.requires_grad for _, p in self._vision_trainables())
+        train_vision = want_dx or (torch.is_grad_enabled() and any(p.requires_grad for _, p in self._vision_trainables()))
         if train_vision:
-            # differentiable vision tower (gava_clip_amd/training.py): gradients of the prompt parameters
+            # differentiable vision tower (gava_clip_amd/training.py): gradients of the prompt parameters and, for an fp32 x
+            # that requires grad (in train() or eval() mode, whatever is frozen), of the clip itself
             from .training import VisionTowerFn
-            cls_x, summary = VisionTowerFn.apply(self, x, clips, *[p for _, p in self._vision_trainables()])
+            cls_x, summary = VisionTowerFn.apply(self, x, clips, input_request, *[p for _, p in self._vision_trainables()])
         else:
             cls_x, summary = self.encode_video(x, clips=clips)
         # The all-gather of the clip embeddings goes out on the main stream as soon as the vision tower is enqueued - BEFORE the

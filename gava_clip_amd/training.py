@@ -24,6 +24,8 @@ VitaCLIP_vision_encoder_utils.py:155-203 in reverse as a list of stages, on scra
                                    summary_ln / summary_attn_layer (wgrad = gava_gemm on transposed operands) and the CLS rows' share
                LN1' of the main rows
     _embedding_backward  ln_pre', sum over tokens = d time_embed
+    _input_backward      only when d x is asked for: patch projection^T (dgrad GEMM), then the fold of the patch rows back into
+                         the clip (gava_unpatchify) - the gradient itself, or a saliency map of it without the gradient in memory
 The second half of the module is the step's tail: similarity head and criterion on the device.
 """
 import ctypes as C
@@ -210,8 +212,12 @@ def pack_vision_backward(model):
         P["w_cls"], P["w_cls_t"] = _both(blk.cls_proj.weight)
         P["b_cls"] = f32(blk.cls_proj.bias)
         layers.append({**P, **_summary_weights(blk)})
+    # patch rows = patches @ Wp^T, Wp = conv weight as [D][3*P*P]: d patches = d rows @ Wp = gemm(d rows, W = Wp^T), its 3*P*P
+    # output columns padded with zero weight rows to the GEMM's granularity of N
+    wp_t = v.patch_embed.proj.weight.detach().float().flatten(1).t()
+    wp_t = torch.nn.functional.pad(wp_t, (0, 0, 0, -wp_t.shape[0] % 128))
     return dict(layers=layers, proj=_bf16(v.proj),     # cls_x = ln_post(x) @ proj (D,E): dx = d @ proj^T = gemm(d, W=proj)
-                summary_ver=model._summary_weight_versions())
+                w_patch_t=_bf16(wp_t), summary_ver=model._summary_weight_versions())
 
 
 def refresh_vision_backward(model, bw):
@@ -393,10 +399,11 @@ def _prompt_backward(P, prm, i, SIDE, dsummary, dX, grads, dgp, d, s):
     dX.view(BT, d.n1, D)[:, 0] += s.dCLS
 
 
-def _embedding_backward(model, d, e0, dX):
+def _embedding_backward(model, d, e0, dX, dx16=None):
     """ln_pre' (in place on dX; e0 is the embedding output it normalised) and the temporal embedding
-    (VitaCLIP_vision_encoder.py:86-100,108-113): time_embed[t] is added to every token of frame t.  -> d time_embed."""
-    hip.layernorm_backward(e0, f32(model.visual.ln_pre.weight), dX, dX)
+    (VitaCLIP_vision_encoder.py:86-100,108-113): time_embed[t] is added to every token of frame t.  -> d time_embed.
+    dx16: receives the bf16 copy of the finished dX (the operand of _input_backward's GEMM)."""
+    hip.layernorm_backward(e0, f32(model.visual.ln_pre.weight), dX, dX, dx16=dx16)
     dte = dX.view(d.B_in, d.T_in, d.n1, d.D).sum(dim=(0, 2))
     if d.T_in != d.T:   # nearest-resized time_embed (VitaCLIP_vision_encoder.py:91-95): row t of the resized table is row floor(t*T/T_in)
         src = (torch.arange(d.T_in, device=d.dev) * d.T) // d.T_in
@@ -404,11 +411,28 @@ def _embedding_backward(model, d, e0, dX):
     return dte
 
 
-def vision_backward(model, saved, dcls_x, B, T, dsummary=None, kept=None):
+def _input_backward(model, bw, d, dx16, mode, x=None):
+    """d(embedding output) -> d x (VitaCLIP_vision_encoder_utils.py:31-53 in reverse).  dx16 [R, D]: the bf16 copy of dX after
+    ln_pre', all B_in*T_in*(n+1) rows in (b, t_in) order.  The embedding is patches @ Wp^T plus terms that do not depend on x
+    (conv bias, pos_embed, time_embed, the cls_token rows), so d patches = dX @ Wp - one dgrad GEMM over every row, the CLS
+    rows included (1/(n+1) of the work, and no gather) - and gava_unpatchify folds the patch rows back into the clip, skipping
+    each frame's CLS row.  mode: hip.UNPATCH_*; GRAD -> fp32 [B_in, 3, T_in, size, size], the map modes -> [B_in, T_in, size,
+    size] (x: the fp32 clip, UNPATCH_GRAD_X_INPUT only).  The product lives for this call only."""
+    sh, w = model._shape, bw["w_patch_t"]
+    dpatch = new(d.dev, d.R, w.shape[0], dtype=torch.float32)
+    hip.gemm(dx16, w, None, dpatch, epilogue=hip.EPI_F32, prec=BWD)
+    shape = (d.B_in, 3, d.T_in) if mode == hip.UNPATCH_GRAD else (d.B_in, d.T_in)
+    out = new(d.dev, *shape, sh["size"], sh["size"], dtype=torch.float32)
+    return hip.unpatchify(dpatch, out, B=d.B_in, T=d.T_in, size=sh["size"], patch=sh["P"], mode=mode, frame_rows=d.n1, row_offset=1, x=x)
+
+
+def vision_backward(model, saved, dcls_x, B, T, dsummary=None, kept=None, input_grad=None):
     """d cls_x (B,E) [+ d summary (B,D), the auxiliary NTE head's input] -> {parameter name: gradient} for the trainable
     vision parameters.  `kept` (alloc_kept, filled by the forward) replaces the per-block recomputation of the main rows:
     activations are then in the forward's operand type (fp16 by default) while gradients stay bf16 - the attention
-    backward converts K/V/Q as it stages them, the QuickGELU' epilogue decodes the pre-activation by its own flag."""
+    backward converts K/V/Q as it stages them, the QuickGELU' epilogue decodes the pre-activation by its own flag.
+    input_grad: None, or dict(mode=hip.UNPATCH_*, x=the fp32 clip or None) - the result then also holds "input", the gradient
+    with respect to the clip or the saliency map of it (_input_backward); without it not one launch differs."""
     bw, v = model._backward_pack("vision"), model.visual
     d = _vision_dims(model, B, T, dcls_x.device)
     if kept is not None:      # block inputs x[i] (x[NL]: the last block's output), embedding output, activations' storage type
@@ -437,7 +461,9 @@ def vision_backward(model, saved, dcls_x, B, T, dsummary=None, kept=None):
         # the CLS rows of dX: it also writes the bf16 copy of the finished dX for the next block
         hip.layernorm_backward(X0, prm.ln[0], s.dxn, dX, accumulate=True, dx16=s.dx16)
     grads["global_prompts"] = dgp
-    grads["time_embed"] = _embedding_backward(model, d, e0, dX)
+    grads["time_embed"] = _embedding_backward(model, d, e0, dX, dx16=s.dx16 if input_grad is not None else None)
+    if input_grad is not None:
+        grads["input"] = _input_backward(model, bw, d, s.dx16, input_grad["mode"], input_grad.get("x"))
     return grads
 
 
@@ -447,14 +473,17 @@ class VisionTowerFn(torch.autograd.Function):
     clips: None, or the uint8 source of VitaCLIP.forward_frames (encode_video's `clips`; x is then the descriptor tensor).
     Either way the backward starts from what the forward kept (the embedding output and the blocks' activations, or in
     recompute mode the fp32 input of every block): the input is read by the forward's patch embedding only, so neither the
-    descriptors nor the decoded videos are held for the backward."""
+    descriptors nor the decoded videos are held for the backward.
+    The backward returns d x when an fp32 x asks for it (never on the uint8 route).  request: None, or the dict of
+    VitaCLIP.saliency - mode (hip.UNPATCH_*) and x; a map mode's result is left in request["out"] instead of being returned
+    (it has not x's shape), so that the full-size gradient is never formed."""
 
     @staticmethod
-    def forward(fctx, model, x, clips, *params):
+    def forward(fctx, model, x, clips, request, *params):
         sh = model._shape
         B, T = (clips[1], clips[2]) if clips is not None else (x.shape[0], x.shape[2])
         n1 = (sh["size"] // sh["P"]) ** 2 + 1
-        fctx.model, fctx.BT = model, (B, T)
+        fctx.model, fctx.BT, fctx.request = model, (B, T), request
         if kept_bytes(model, B, T) <= model.keep_activation_bytes:
             fctx.kept = alloc_kept(model, B, T, x.device)
             cls_x, summary = model.encode_video(x, kept=fctx.kept, clips=clips)
@@ -473,13 +502,19 @@ class VisionTowerFn(torch.autograd.Function):
         dev = (kept["x"] if kept is not None else saved).device
         if dcls_x is None:
             dcls_x = torch.zeros(fctx.BT[0], model._shape["E"], device=dev)
-        g = vision_backward(model, saved, dcls_x.contiguous(), *fctx.BT, dsummary=dsummary, kept=kept)
-        fctx.kept = None      # release the activation buffers with the graph
+        req = None
+        if fctx.needs_input_grad[1]:      # (never on the uint8 route: its x is the descriptor tensor)
+            req = fctx.request if fctx.request is not None else dict(mode=hip.UNPATCH_GRAD)
+        g = vision_backward(model, saved, dcls_x.contiguous(), *fctx.BT, dsummary=dsummary, kept=kept, input_grad=req)
+        fctx.kept = fctx.request = None      # release the activation buffers with the graph
+        dx = g.get("input")
+        if dx is not None and req["mode"] != hip.UNPATCH_GRAD:
+            req["out"], dx = dx, None
         out = []
         for name, p in model._vision_trainables():
             gi = g.get(name)
             out.append(gi.reshape(p.shape).to(p.dtype) if (gi is not None and p.requires_grad) else None)
-        return (None, None, None, *out)
+        return (None, dx, None, None, *out)
 
 
 # =================================================================================================

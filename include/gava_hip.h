@@ -773,6 +773,40 @@ int gava_adamw_step(const gava_adamw_args* a, gava_stream_t stream);
  * min(cap, 3) entries, returns 3. */
 int gava_optim_struct_sizes(size_t* out, int cap);
 
+/* ---- gradient with respect to the input clip: the fold half of ImagePatchEmbed2D ----------------------------------------------
+ *
+ * The transpose of gava_patchify's index map, as one HBM-bound pass over fp32 data.  dpatch is d(embedding rows) x the patch
+ * weight: fp32, B*T frames of frame_rows rows each, rows ld floats apart.  Of every frame the kernel reads the n = (size/P)^2
+ * rows row_offset ... row_offset + n - 1 (frame_rows = n + 1, row_offset = 1 skips the CLS row of the embedding output;
+ * frame_rows = n, row_offset = 0 is the dense form) and of every row the columns [0, 3*P*P): columns [3*P*P, ld) are the GEMM's
+ * padding and are never read.  With g(b, c, t, py*P + ky, px*P + kx) = dpatch[(b*T + t) * frame_rows + row_offset + py*(size/P) + px]
+ * [c*P*P + ky*P + kx]:
+ *   GAVA_UNPATCH_GRAD          out fp32 [B][3][T][size][size] = g: a permutation of the input values, bit for bit
+ *   GAVA_UNPATCH_ABSMAX        out fp32 [B][T][size][size]    = max over c of |g|
+ *   GAVA_UNPATCH_L2            out                            = sqrt(g_0^2 + g_1^2 + g_2^2)
+ *   GAVA_UNPATCH_GRAD_X_INPUT  out                            = g_0 x_0 + g_1 x_1 + g_2 x_2, x the fp32 clip [B][3][T][size][size]
+ * The channel sums run in the order c = 0, 1, 2 in fp32 (fused multiply-adds, a correctly rounded square root); no atomics, so
+ * a call repeats bit for bit.  The three map modes never form the [B][3][T][size][size] gradient.  One workgroup owns P whole
+ * image rows of a frame: its stores are contiguous rows, its loads P-float segments; 16-byte accesses when P and ld are
+ * multiples of 4, 8-byte when they are even (P = 14), single floats otherwise.  Any number of frames goes in one launch.
+ * GAVA_EINVAL, before any launch: null args, a null dpatch or out, a pointer (x included) that is not 16-byte aligned,
+ * B, T, size or patch < 1 or B*T past 2^31 - 1, size % patch != 0, ld < 3*patch*patch, row_offset < 0 or
+ * row_offset + n > frame_rows, a mode outside the four, x given in a mode other than GRAD_X_INPUT or missing in it. */
+#define GAVA_UNPATCH_GRAD 0
+#define GAVA_UNPATCH_ABSMAX 1
+#define GAVA_UNPATCH_L2 2
+#define GAVA_UNPATCH_GRAD_X_INPUT 3
+typedef struct {
+  const float* dpatch; int64_t ld;
+  const float* x;                      /* GAVA_UNPATCH_GRAD_X_INPUT only, NULL otherwise */
+  float* out;
+  int B, T, size, patch, mode, frame_rows, row_offset, reserved;
+} gava_unpatchify_args;
+int gava_unpatchify(const gava_unpatchify_args* a, gava_stream_t stream);
+
+/* sizeof of gava_unpatchify_args, like gava_optim_struct_sizes.  Writes min(cap, 1) entries, returns 1. */
+int gava_input_grad_struct_sizes(size_t* out, int cap);
+
 /* sizeof of every ABI struct as the library was compiled, in the order gemm_args, layernorm_args, attention_args,
  * attention_f32_args, clip_desc, vision_layer, vision_layer8, vision_model, text_layer, text_model, layernorm_bwd_args,
  * attention_bwd_args, vision_saved, preprocess_args, patchify_args, preprocess_clips_args, view_scores_args.  Writes
