@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from gava_clip_amd import hip
+from attention_ref import ref_attention, side_index   # the gather and the fp64 forward, shared with the edge tests
 
 pytestmark = pytest.mark.gpu
 
@@ -27,27 +28,6 @@ def dev():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     return torch.device("cuda")
-
-
-def side_index(BT, T, G, device):
-    """[BT][G + T + 1] rows of the side matrix that frame f attends to (gava_attention's layout)."""
-    f = torch.arange(BT, device=device)
-    glob = torch.arange(G, device=device).expand(BT, G)
-    loc = G + (f // T * T)[:, None] + torch.arange(T, device=device)[None]
-    return torch.cat([glob, loc, (G + BT + f)[:, None]], 1)
-
-
-def ref_attention(q, k, v, side, BT, T, G, n, heads, nq):
-    """fp64: q [BT][nq][D] (pre-scaled), k / v [BT][n][D], side [G + 2 BT][2D] or None -> [BT][nq][D]."""
-    D = heads * 64
-    if side is not None:
-        idx = side_index(BT, T, G, q.device)
-        k = torch.cat([k, side[idx, :D]], 1)
-        v = torch.cat([v, side[idx, D:]], 1)
-    qh = q.double().view(BT, nq, heads, 64).transpose(1, 2)
-    kh = k.double().view(BT, -1, heads, 64).transpose(1, 2)
-    vh = v.double().view(BT, -1, heads, 64).transpose(1, 2)
-    return ((qh @ kh.transpose(-1, -2)).softmax(-1) @ vh).transpose(1, 2).reshape(BT, nq, D)
 
 
 def make(BT, G, n, heads, prec, seed):
