@@ -34,7 +34,9 @@ EXPORTS = ["gava_abi_version", "gava_gemm", "gava_layernorm", "gava_attention",
            "gava_sigmoid_criterion", "gava_sigmoid_criterion_backward", "gava_nte_diag_loss", "gava_nte_diag_loss_backward",
            "gava_aux_struct_sizes",
            "gava_adamw_plan", "gava_adamw_step", "gava_optim_struct_sizes",
-           "gava_unpatchify", "gava_input_grad_struct_sizes"]
+           "gava_unpatchify", "gava_input_grad_struct_sizes",
+           "gava_attention_mass", "gava_attention_maps_struct_sizes"]
+ATTENTION_MASS_MAX_KEYS = 640     # gava_attention_mass keeps K of one (frame, head) resident in LDS
 ADAMW_MAX_GROUPS = 8
 
 _vp, _fp, _ip = C.c_void_p, C.c_void_p, C.c_void_p  # all device pointers travel as void*
@@ -226,6 +228,14 @@ class UnpatchifyArgs(C.Structure):
                 ("frame_rows", C.c_int), ("row_offset", C.c_int), ("reserved", C.c_int)]
 
 
+class AttentionMassArgs(C.Structure):
+    _fields_ = [("q", _vp), ("k", _vp), ("ld_qkv", C.c_int64), ("side_k", _vp), ("ld_side", C.c_int64),
+                ("w", _fp), ("out", _fp),
+                ("batch", C.c_int), ("heads", C.c_int), ("n_q", C.c_int), ("n_kmain", C.c_int),
+                ("n_g", C.c_int), ("T", C.c_int), ("has_summary", C.c_int), ("renorm", C.c_int), ("prec", C.c_int),
+                ("q_batch_rows", C.c_int), ("ld_q", C.c_int64)]
+
+
 class VisionSaved(C.Structure):
     _fields_ = [("e0", _fp), ("x", _fp), ("x1", _fp), ("qkv", _vp), ("pre", _vp), ("sidekv", _vp),
                 ("last_q", _vp), ("last_x1", _fp), ("last_pre", _vp)]
@@ -397,6 +407,16 @@ def load():
     if lib.gava_input_grad_struct_sizes(sizes, len(input_grad_mirrors)) != len(input_grad_mirrors):
         raise GavaError("libgava_hip.so and gava_clip_amd/hip.py disagree on the number of input-gradient ABI structs")
     for cls, sz in zip(input_grad_mirrors, sizes):
+        if C.sizeof(cls) != sz:
+            raise GavaError(f"ctypes mirror {cls.__name__} is {C.sizeof(cls)} bytes, the library's struct {sz}: gava_clip_amd/hip.py is out of "
+                            f"step with include/gava_hip.h")
+    # the attention maps' struct, the same way
+    maps_mirrors = [AttentionMassArgs]
+    lib.gava_attention_mass.argtypes, lib.gava_attention_mass.restype = [C.POINTER(AttentionMassArgs), _vp], C.c_int
+    lib.gava_attention_maps_struct_sizes.argtypes, lib.gava_attention_maps_struct_sizes.restype = [C.POINTER(C.c_size_t), C.c_int], C.c_int
+    if lib.gava_attention_maps_struct_sizes(sizes, len(maps_mirrors)) != len(maps_mirrors):
+        raise GavaError("libgava_hip.so and gava_clip_amd/hip.py disagree on the number of attention-map ABI structs")
+    for cls, sz in zip(maps_mirrors, sizes):
         if C.sizeof(cls) != sz:
             raise GavaError(f"ctypes mirror {cls.__name__} is {C.sizeof(cls)} bytes, the library's struct {sz}: gava_clip_amd/hip.py is out of "
                             f"step with include/gava_hip.h")
@@ -608,6 +628,38 @@ def unpatchify(dpatch, out, *, B, T, size, patch, mode, frame_rows, row_offset, 
     a.B, a.T, a.size, a.patch, a.mode, a.frame_rows, a.row_offset = B, T, size, patch, mode, frame_rows, row_offset
     with torch.cuda.device(out.device):
         check(load().gava_unpatchify(C.byref(a), stream_ptr(out.device)), "gava_unpatchify")
+    return out
+
+
+def attention_mass(q, k, out=None, *, batch, heads, n_q, n_kmain, prec, w=None, renorm=False,
+                   side_k=None, n_g=0, T=0, has_summary=False, q_batch_rows=0):
+    """Where the attention goes (gava_attention_mass): out[f, h, j] = sum_i w[f, i] * softmax_j(q_i . k_j), operands addressed
+    as by `attention` (q pre-scaled h16, possibly a buffer of its own with q_batch_rows rows per frame; side_k = the prompt
+    rows' keys).  renorm: P restricted to the frame's own n_kmain keys and renormalised per query.  w: fp32 [batch, n_q] or
+    None (all ones).  -> out fp32 [batch, heads, n_kmain (renorm) or n_kmain + n_side], allocated when not given.  One
+    launch, no sync; at most ATTENTION_MASS_MAX_KEYS keys."""
+    for name, t in (("q", q), ("k", k), ("side_k", side_k), ("w", w), ("out", out)):
+        _require(t is None or (torch.is_tensor(t) and t.is_cuda), f"attention_mass: {name} must be on the HIP device: there is no CPU fallback")
+    n_side = (n_g + T + int(bool(has_summary))) if side_k is not None else 0
+    n_out = n_kmain if renorm else n_kmain + n_side
+    _require(n_kmain + n_side <= ATTENTION_MASS_MAX_KEYS,
+             f"attention_mass: {n_kmain + n_side} keys, at most {ATTENTION_MASS_MAX_KEYS} are supported")
+    _require(w is None or (w.dtype == torch.float32 and w.is_contiguous() and w.numel() == batch * n_q),
+             "attention_mass: w must be a contiguous fp32 [batch, n_q] tensor")
+    if out is None:
+        out = torch.empty(batch, heads, n_out, dtype=torch.float32, device=q.device)
+    _require(out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (batch, heads, n_out),
+             f"attention_mass: out must be a contiguous fp32 {(batch, heads, n_out)} tensor")
+    a = AttentionMassArgs()
+    a.q, a.k, a.ld_qkv = ptr(q), ptr(k), k.stride(0)
+    a.side_k, a.ld_side = ptr(side_k), (side_k.stride(0) if side_k is not None else 0)
+    a.w, a.out = ptr(w), ptr(out)
+    a.batch, a.heads, a.n_q, a.n_kmain = batch, heads, n_q, n_kmain
+    a.n_g, a.T, a.has_summary = (n_g, T, int(bool(has_summary))) if side_k is not None else (0, 0, 0)
+    a.renorm, a.prec = int(bool(renorm)), prec
+    a.q_batch_rows, a.ld_q = q_batch_rows, (q.stride(0) if q_batch_rows else 0)
+    with torch.cuda.device(out.device):
+        check(load().gava_attention_mass(C.byref(a), stream_ptr(out.device)), "gava_attention_mass")
     return out
 
 

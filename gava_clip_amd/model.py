@@ -826,6 +826,26 @@ class _StandaloneHost(_HipHost):
 
 
 # ---------------------------------------------------------------------------------------------
+class AttentionMaps:
+    """What VitaCLIP.attention_maps returns: fp32 device tensors, B clips of T frames as given.
+      mode, layer          what was asked for (layer: the block's index from 0; None for "rollout")
+      patches [B, T, g, g] the CLS token's attention (or rollout) on the frame's patches, g = S / P
+      cls     [B, T]       ... on the CLS token itself
+      logits  [B, C]       the inference head on this forward's features
+    and for mode "cls" (None for "rollout"; with heads=None every map carries a head axis after T):
+      global_prompts [B, T, G], local_prompts [B, T, num_frames] (frame t's CLS on the local prompt of frame t' of its
+      num_frames group), summary [B, T]; the five groups of a frame sum to 1."""
+    __slots__ = ("mode", "layer", "patches", "cls", "logits", "global_prompts", "local_prompts", "summary")
+
+    def __init__(self, mode, layer, patches, cls, logits, global_prompts=None, local_prompts=None, summary=None):
+        self.mode, self.layer, self.patches, self.cls, self.logits = mode, layer, patches, cls, logits
+        self.global_prompts, self.local_prompts, self.summary = global_prompts, local_prompts, summary
+
+    def __repr__(self):
+        shapes = ", ".join(f"{k}={tuple(getattr(self, k).shape)}" for k in self.__slots__[2:] if getattr(self, k) is not None)
+        return f"AttentionMaps(mode={self.mode!r}, layer={self.layer!r}, {shapes})"
+
+
 class VitaCLIP(nn.Module, _HipHost):
 
     def __init__(
@@ -1211,6 +1231,127 @@ class VitaCLIP(nn.Module, _HipHost):
         if torch.is_tensor(self.text_features) and self.text_features.requires_grad:
             self.text_features = self.text_features.detach()        # the last reference into this call's graph
         return (dx if mode == hip.UNPATCH_GRAD else request.pop("out")), logits.detach(), target
+
+    def attention_maps(self, x, mode="rollout", layer=-1, heads="mean", max_clips=None):
+        """What the CLS token of every frame attends to -> AttentionMaps (see there for the fields).
+          mode="rollout"  attention rollout of the CLS token through all blocks: row 0 of A^_L ... A^_1, A^_l = (I + mean_h
+                          A_l,h) / 2, A_l,h = block l's probabilities restricted to the frame's own tokens (CLS + patches) and
+                          renormalised per row - the prompt tokens are rebuilt in every block and carry no path between
+                          blocks.  Run as a vector chain from the last block to the first (gava_attention_mass, one launch
+                          per block; no matrix product).  patches + cls sum to 1 per frame.  `layer` is ignored, `heads`
+                          must be "mean".
+          mode="cls"      the CLS row of block `layer` (negative: from the end) over ALL its keys, split by key group:
+                          patches, cls, global_prompts, local_prompts, summary; heads="mean" averages over the heads,
+                          heads=None keeps them as an axis after T.
+        x: a device clip batch [B, 3, T, S, S] as forward() takes it (decoded uint8 videos: `preprocessor.batch(videos)`
+        first).  T need not be num_frames: the blocks regroup the B*T frames by the model's num_frames, and so do the local
+        prompts' columns.
+        The clips run through the activation-keeping forward of the training path (encode_video(kept=...)) under no_grad,
+        in chunks of whole num_frames groups whose kept activations (training.kept_bytes) fit keep_activation_bytes;
+        max_clips sets the clips per chunk instead.  The buffers are reused from chunk to chunk.  `logits` come from the
+        inference head on THIS forward's features: the kept forward packs its operands plainly (no weight-lo pass, no
+        16-bit residual pair), so they can differ from forward()'s within the operand rounding.
+        Works in eval() and train() mode; no .grad is touched, no graph is left, nothing waits for the device.  With an
+        initialised process group every rank keeps its own clips.  A per-descriptor (use_descriptor) head is refused."""
+        from . import training
+        if mode not in ("rollout", "cls"):
+            raise hip.GavaError(f"attention_maps: mode must be 'rollout' or 'cls', got {mode!r}")
+        if heads not in ("mean", None):
+            raise hip.GavaError(f"attention_maps: heads must be 'mean' or None, got {heads!r}")
+        if mode == "rollout" and heads is None:
+            raise hip.GavaError("attention_maps: rollout averages over the heads in every block (heads='mean'); per-head maps are mode='cls'")
+        sh, Tm = self._shape, self.num_frames
+        NL, D, H, G = sh["layers"], sh["D"], sh["H"], sh["G"]
+        if mode == "cls":
+            if not (isinstance(layer, int) and -NL <= layer < NL):
+                raise hip.GavaError(f"attention_maps: layer {layer!r} is outside the {NL} blocks")
+            layer = layer % NL
+        else:
+            layer = None
+        if not (torch.is_tensor(x) and x.dim() == 5 and x.is_floating_point() and x.shape[1] == 3 and x.shape[3] == x.shape[4] == sh["size"]):
+            raise hip.GavaError(f"attention_maps takes a floating-point clip batch [B, 3, T, {sh['size']}, {sh['size']}], got "
+                                f"{(x.dtype, tuple(x.shape)) if torch.is_tensor(x) else type(x)}")
+        if not x.is_cuda:
+            raise hip.GavaError("VitaCLIP (gava_clip_amd) runs on the HIP device only: move the model and the "
+                                "input with .cuda(); there is no CPU fallback")
+        if self.use_text_prompt_learning and self.prompt_learner.n_kv is None:
+            raise hip.GavaError("attention_maps: a per-descriptor (use_descriptor / desc_wise) head has no single logit per class")
+        B, T = x.shape[0], x.shape[2]
+        unit = Tm // math.gcd(T, Tm)                  # the fewest clips that are whole num_frames groups
+        if B == 0 or B % unit:
+            raise hip.GavaError(f"attention_maps: {B} clips of {T} frames are not whole groups of num_frames = {Tm}")
+        g = sh["size"] // sh["P"]
+        n1 = g * g + 1
+        n_all = n1 + G + Tm + 1
+        if n_all > hip.ATTENTION_MASS_MAX_KEYS:
+            raise hip.GavaError(f"attention_maps: {n_all} keys per frame, gava_attention_mass takes at most {hip.ATTENTION_MASS_MAX_KEYS}")
+        if max_clips is None:
+            step = B // unit * unit
+            while step > unit and training.kept_bytes(self, step, T) > self.keep_activation_bytes:
+                step = (step // unit + 1) // 2 * unit
+        else:
+            step = min(B, max(int(max_clips) // unit * unit, unit))
+        dev = x.device
+        mass = dict(heads=H, n_kmain=n1, prec=self.prec, n_g=G, T=Tm, has_summary=True)
+        with torch.cuda.device(dev), torch.no_grad():
+            self._attach_encoders()
+            self._pack()
+            kept = training.alloc_kept(self, step, T, dev)
+            video = torch.empty(B, sh["E"], dtype=torch.float32, device=dev)
+            maps = torch.empty((B * T, n1) if mode == "rollout" else (B * T, H, n_all), dtype=torch.float32, device=dev)
+            for i in range(0, B, step):
+                nb = min(step, B - i)
+                kb = kept
+                if nb != step:          # the last, smaller chunk: the same memory under that chunk's shapes
+                    shapes = {k: v.shape for k, v in training.alloc_kept(self, nb, T, "meta").items()}
+                    kb = {k: kept[k].view(-1)[:math.prod(shp)].view(shp) for k, shp in shapes.items()}
+                video[i:i + nb] = self.encode_video(x[i:i + nb], kept=kb)[0]
+                BT = nb * T
+                keys = lambda l: dict(k=kb["qkv"][l][:, D:2 * D], side_k=kb["sidekv"][l][:, :D])
+                out = maps[i * T:(i + nb) * T]
+                if mode == "cls":
+                    if layer == NL - 1:     # the kept last block has its CLS queries only, in a buffer of their own
+                        hip.attention_mass(kb["last_q"], out=out, batch=BT, n_q=1, q_batch_rows=1, **keys(layer), **mass)
+                    else:
+                        hip.attention_mass(kb["qkv"][layer][:, :D], out=out, batch=BT, n_q=1, q_batch_rows=n1, **keys(layer), **mass)
+                    continue
+                r = hip.attention_mass(kb["last_q"], batch=BT, n_q=1, q_batch_rows=1, renorm=True, **keys(NL - 1), **mass).mean(1).mul_(0.5)
+                r[:, 0] += 0.5              # r = e_cls / 2 + mean_h A_L[0] / 2
+                for l in range(NL - 2, -1, -1):
+                    o = hip.attention_mass(kb["qkv"][l][:, :D], batch=BT, n_q=n1, w=r, renorm=True, **keys(l), **mass)
+                    r = (0.5 * r).add_(o.mean(1), alpha=0.5)
+                out.copy_(r)
+            logits = self._maps_logits(video)
+        if mode == "rollout":
+            m = maps.view(B, T, n1)
+            return AttentionMaps(mode, None, m[..., 1:].reshape(B, T, g, g), m[..., 0], logits)
+        m = (maps.mean(1) if heads == "mean" else maps).view(B, T, *(() if heads == "mean" else (H,)), n_all)
+        return AttentionMaps(mode, layer, m[..., 1:n1].reshape(*m.shape[:-1], g, g), m[..., 0], logits,
+                             global_prompts=m[..., n1:n1 + G], local_prompts=m[..., n1 + G:n1 + G + Tm], summary=m[..., n_all - 1])
+
+    def _maps_logits(self, video):
+        """The inference head (gava_similarity_head) on this rank's clip features; text features from the cache when it is
+        valid, else from the text tower on the current stream.  Leaves text_features, the cache and `last` alone."""
+        dev, sh = video.device, self._shape
+        if self.use_text_prompt_learning:
+            pl_params = list(self.prompt_learner.parameters())
+            key = ((self._pack_key(), tuple(q._version for q in pl_params), tuple(q.data_ptr() for q in pl_params))
+                   if (self.cache_text_features and not self.training) else None)
+            hit = key is not None and self._text_cache is not None and self._text_cache[0] == key
+            text = self._text_cache[1] if hit else self.encode_text()
+            n_kv = self.prompt_learner.n_kv
+        else:
+            text, n_kv = self.text_features.detach().to(device=dev, dtype=torch.float32).contiguous(), 1
+        Bg, n_cls = video.shape[0], text.shape[0] // n_kv
+        logits = torch.empty(Bg, n_cls, dtype=torch.float32, device=dev)
+        tfeat = torch.empty(n_cls, sh["E"], dtype=torch.float32, device=dev)
+        vnorm = torch.empty(Bg, sh["E"], dtype=torch.float32, device=dev)
+        ls = self.logit_scale.detach().float().reshape(1)
+        lb = self.logit_bias.detach().float().reshape(1) if self.logit_bias is not None else None
+        hip.check(hip.load().gava_similarity_head(hip.ptr(video), hip.ptr(text), hip.ptr(ls), hip.ptr(lb), Bg, n_cls, n_kv,
+                                                  sh["E"], hip.ptr(logits), hip.ptr(tfeat), hip.ptr(vnorm), hip.stream_ptr(dev)),
+                  "gava_similarity_head")
+        return logits
 
     def _forward_impl(self, x, memory, video_nte, desc_wise, clips=None, input_request=None):
         lib = hip.load()

@@ -807,6 +807,45 @@ int gava_unpatchify(const gava_unpatchify_args* a, gava_stream_t stream);
 /* sizeof of gava_unpatchify_args, like gava_optim_struct_sizes.  Writes min(cap, 1) entries, returns 1. */
 int gava_input_grad_struct_sizes(size_t* out, int cap);
 
+/* ---- attention maps: where a vision block's attention goes -------------------------------------------------------------------
+ *
+ * The probabilities softmax(Q K^T) of Attention.forward (VitaCLIP_vision_encoder_utils.py:71-77), which gava_attention never
+ * writes, summed over the queries with a weight.  Operands are addressed as by gava_attention: problem (f, h) = frame f,
+ * head h (columns [64h, 64h + 64)); q is h16 and already carries the 1/sqrt(64) factor, queries are rows f*q_batch_rows +
+ * [0, n_q) of q with row stride ld_q (defaults, when 0: q_batch_rows = n_q, ld_q = ld_qkv); the keys are the n_kmain rows
+ * f*n_kmain + [0, n_kmain) of k followed by the side rows [n_g global | T local of the frame's clip | summary] of side_k, in
+ * gava_attention's layout (n_g + batch + batch rows; n_g = T = has_summary = 0: no side rows).  With
+ *   P[i][j] = softmax_j(q_i . k_j) over all n_keys = n_kmain + n_side keys,
+ *   renorm = 0:  out[f][h][j] = sum_i w[f][i] * P[i][j]                                   j in [0, n_keys)
+ *   renorm = 1:  out[f][h][j] = sum_i w[f][i] * P[i][j] / sum_{j' < n_kmain} P[i][j']     j in [0, n_kmain)
+ * (renorm = 1 is the softmax over the frame's own keys alone, and is computed as that: the side rows are then not read.)
+ * w: fp32 [batch][n_q], NULL = every weight 1 (the same bits as an array of ones).  out: fp32 [batch][heads][n_out],
+ * n_out = n_keys or n_kmain.  n_q = 1 with w = NULL is the CLS row of a block (the only form a kept last block allows: its
+ * queries are gava_vision_saved.last_q, its keys columns D..2D of its qkv slot); n_q = n_kmain with renorm = 1 is one step of
+ * the attention-rollout chain r <- r/2 + mean_h(out)/2.
+ * Scores are MFMA products accumulated in fp32, the softmax is fp32 in exp2 form, nothing is rounded to 16 bits.  Every
+ * output element is summed by one wave in a fixed order (queries ascending per lane, then a fixed butterfly over sixteen
+ * lanes): no atomics, two runs give the same bits.  One launch on `stream`.
+ * Limits: K of one (frame, head) is resident in LDS, so n_keys <= 640 in either form (594 keys = 384 px at P = 16 with T = 8, G = 8);
+ * n_q <= n_kmain.  GAVA_EINVAL, before any launch: beyond those limits, null args / q / k / out, batch, heads, n_q or
+ * n_kmain < 1, ld_qkv / ld_side / ld_q not a multiple of 8 or below heads*64, q / k / side_k not 16-byte aligned, w / out not
+ * 4-byte aligned, side rows asked for without side_k or with batch % T != 0, q_batch_rows < n_q, renorm outside {0, 1}, an
+ * unknown prec. */
+typedef struct {
+  const void* q; const void* k; int64_t ld_qkv;     /* h16, element strides */
+  const void* side_k; int64_t ld_side;
+  const float* w;                                   /* fp32 [batch][n_q] or NULL */
+  float* out;                                       /* fp32 [batch][heads][renorm ? n_kmain : n_kmain + n_side] */
+  int batch, heads, n_q, n_kmain;
+  int n_g, T, has_summary;
+  int renorm, prec;
+  int q_batch_rows; int64_t ld_q;
+} gava_attention_mass_args;
+int gava_attention_mass(const gava_attention_mass_args* a, gava_stream_t stream);
+
+/* sizeof of gava_attention_mass_args, like gava_input_grad_struct_sizes.  Writes min(cap, 1) entries, returns 1. */
+int gava_attention_maps_struct_sizes(size_t* out, int cap);
+
 /* sizeof of every ABI struct as the library was compiled, in the order gemm_args, layernorm_args, attention_args,
  * attention_f32_args, clip_desc, vision_layer, vision_layer8, vision_model, text_layer, text_model, layernorm_bwd_args,
  * attention_bwd_args, vision_saved, preprocess_args, patchify_args, preprocess_clips_args, view_scores_args.  Writes
