@@ -10,6 +10,9 @@ def __getattr__(name):  # lazy: importing the package must not need torch/HIP
     if name == "VitaCLIP":
         from .model import VitaCLIP
         return VitaCLIP
+    if name == "RelevanceMaps":
+        from .model import RelevanceMaps
+        return RelevanceMaps
     if name == "TrainCriterion":
         from .training import TrainCriterion
         return TrainCriterion

@@ -35,8 +35,10 @@ EXPORTS = ["gava_abi_version", "gava_gemm", "gava_layernorm", "gava_attention",
            "gava_aux_struct_sizes",
            "gava_adamw_plan", "gava_adamw_step", "gava_optim_struct_sizes",
            "gava_unpatchify", "gava_input_grad_struct_sizes",
-           "gava_attention_mass", "gava_attention_maps_struct_sizes"]
+           "gava_attention_mass", "gava_attention_maps_struct_sizes",
+           "gava_attention_relevance", "gava_attention_relevance_struct_sizes"]
 ATTENTION_MASS_MAX_KEYS = 640     # gava_attention_mass keeps K of one (frame, head) resident in LDS
+ATTENTION_RELEVANCE_MAX_KEYS = 640     # and so does gava_attention_relevance
 ADAMW_MAX_GROUPS = 8
 
 _vp, _fp, _ip = C.c_void_p, C.c_void_p, C.c_void_p  # all device pointers travel as void*
@@ -236,6 +238,15 @@ class AttentionMassArgs(C.Structure):
                 ("q_batch_rows", C.c_int), ("ld_q", C.c_int64)]
 
 
+class AttentionRelevanceArgs(C.Structure):
+    _fields_ = [("q", _vp), ("k", _vp), ("v", _vp), ("ld_qkv", C.c_int64), ("side_k", _vp), ("ld_side", C.c_int64),
+                ("dout", _vp), ("ld_dout", C.c_int64), ("w", _fp), ("out", _fp),
+                ("batch", C.c_int), ("heads", C.c_int), ("n_q", C.c_int), ("n_kmain", C.c_int),
+                ("n_g", C.c_int), ("T", C.c_int), ("has_summary", C.c_int),
+                ("prec", C.c_int), ("act_prec_set", C.c_int), ("act_prec", C.c_int),
+                ("q_batch_rows", C.c_int), ("reserved", C.c_int), ("ld_q", C.c_int64)]
+
+
 class VisionSaved(C.Structure):
     _fields_ = [("e0", _fp), ("x", _fp), ("x1", _fp), ("qkv", _vp), ("pre", _vp), ("sidekv", _vp),
                 ("last_q", _vp), ("last_x1", _fp), ("last_pre", _vp)]
@@ -417,6 +428,16 @@ def load():
     if lib.gava_attention_maps_struct_sizes(sizes, len(maps_mirrors)) != len(maps_mirrors):
         raise GavaError("libgava_hip.so and gava_clip_amd/hip.py disagree on the number of attention-map ABI structs")
     for cls, sz in zip(maps_mirrors, sizes):
+        if C.sizeof(cls) != sz:
+            raise GavaError(f"ctypes mirror {cls.__name__} is {C.sizeof(cls)} bytes, the library's struct {sz}: gava_clip_amd/hip.py is out of "
+                            f"step with include/gava_hip.h")
+    # the relevance step's struct, the same way
+    relevance_mirrors = [AttentionRelevanceArgs]
+    lib.gava_attention_relevance.argtypes, lib.gava_attention_relevance.restype = [C.POINTER(AttentionRelevanceArgs), _vp], C.c_int
+    lib.gava_attention_relevance_struct_sizes.argtypes, lib.gava_attention_relevance_struct_sizes.restype = [C.POINTER(C.c_size_t), C.c_int], C.c_int
+    if lib.gava_attention_relevance_struct_sizes(sizes, len(relevance_mirrors)) != len(relevance_mirrors):
+        raise GavaError("libgava_hip.so and gava_clip_amd/hip.py disagree on the number of relevance ABI structs")
+    for cls, sz in zip(relevance_mirrors, sizes):
         if C.sizeof(cls) != sz:
             raise GavaError(f"ctypes mirror {cls.__name__} is {C.sizeof(cls)} bytes, the library's struct {sz}: gava_clip_amd/hip.py is out of "
                             f"step with include/gava_hip.h")
@@ -660,6 +681,52 @@ def attention_mass(q, k, out=None, *, batch, heads, n_q, n_kmain, prec, w=None, 
     a.q_batch_rows, a.ld_q = q_batch_rows, (q.stride(0) if q_batch_rows else 0)
     with torch.cuda.device(out.device):
         check(load().gava_attention_mass(C.byref(a), stream_ptr(out.device)), "gava_attention_mass")
+    return out
+
+
+def attention_relevance(q, k, v, dout, out=None, *, batch, heads, n_q, n_kmain, prec, w=None, act_prec=None,
+                        side_k=None, n_g=0, T=0, has_summary=False, q_batch_rows=0):
+    """One step of gradient-weighted attention relevance (gava_attention_relevance): out[f, h, j] = sum_i w[f, i] *
+    max(0, P[i, j] * G[i, j]) over the frame's own n_kmain keys, P = softmax_j(q_i . k_j) over ALL keys (side_k = the prompt
+    rows' keys, not renormalised), G[i, j] = dout_i . v_j per head.  q / k / v / side_k are h16 of act_prec (None: of prec), q
+    pre-scaled; dout is h16 of prec.  With q_batch_rows, q and dout are buffers of their own holding q_batch_rows rows per
+    frame.  w: fp32 [batch, n_q] or None (all ones).  -> out fp32 [batch, heads, n_kmain], allocated when not given.  One
+    launch, no sync; at most ATTENTION_RELEVANCE_MAX_KEYS keys."""
+    for name, t in (("q", q), ("k", k), ("v", v), ("dout", dout), ("side_k", side_k), ("w", w), ("out", out)):
+        _require(t is None or (torch.is_tensor(t) and t.is_cuda), f"attention_relevance: {name} must be on the HIP device: there is no CPU fallback")
+    n_side = (n_g + T + int(bool(has_summary))) if side_k is not None else 0
+    _require(n_kmain + n_side <= ATTENTION_RELEVANCE_MAX_KEYS,
+             f"attention_relevance: {n_kmain + n_side} keys, at most {ATTENTION_RELEVANCE_MAX_KEYS} are supported")
+    _require(0 < n_q <= n_kmain and (q_batch_rows == 0 or q_batch_rows >= n_q), f"attention_relevance: n_q={n_q} n_kmain={n_kmain} q_batch_rows={q_batch_rows}")
+    act = prec if act_prec is None else act_prec
+    _require(prec in PREC_TORCH and act in PREC_TORCH, f"attention_relevance: unknown prec {prec!r} / act_prec {act_prec!r}")
+    for name, t in (("q", q), ("k", k), ("v", v), ("side_k", side_k)):
+        _require(t is None or (t.dtype == PREC_TORCH[act] and t.dim() == 2 and t.stride(1) == 1), f"attention_relevance: {name} must be {PREC_TORCH[act]} rows")
+    _require(dout.dtype == PREC_TORCH[prec] and dout.dim() == 2 and dout.stride(1) == 1, f"attention_relevance: dout must be {PREC_TORCH[prec]} rows")
+    qrows = batch * (q_batch_rows or n_q)
+    _require(q.shape[0] >= qrows and dout.shape[0] >= qrows and min(q.shape[1], dout.shape[1]) >= heads * 64,
+             f"attention_relevance: q {tuple(q.shape)} / dout {tuple(dout.shape)} hold no {qrows} rows of {heads} heads")
+    _require(k.shape[0] >= batch * n_kmain and v.shape[0] >= batch * n_kmain and k.stride(0) == v.stride(0) and min(k.shape[1], v.shape[1]) >= heads * 64
+             and (q_batch_rows or q.stride(0) == k.stride(0)),
+             f"attention_relevance: k {tuple(k.shape)} / v {tuple(v.shape)} are not {batch * n_kmain} rows of one row stride")
+    _require(side_k is None or (T > 0 and batch % T == 0 and side_k.shape[0] >= n_g + 2 * batch and side_k.shape[1] >= heads * 64),
+             "attention_relevance: side_k must hold n_g + 2 * batch rows, batch whole clips of T frames")
+    _require(w is None or (w.dtype == torch.float32 and w.is_contiguous() and w.numel() == batch * n_q),
+             "attention_relevance: w must be a contiguous fp32 [batch, n_q] tensor")
+    if out is None:
+        out = torch.empty(batch, heads, n_kmain, dtype=torch.float32, device=q.device)
+    _require(out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (batch, heads, n_kmain),
+             f"attention_relevance: out must be a contiguous fp32 {(batch, heads, n_kmain)} tensor")
+    a = AttentionRelevanceArgs()
+    a.q, a.k, a.v, a.ld_qkv = ptr(q), ptr(k), ptr(v), k.stride(0)
+    a.side_k, a.ld_side = ptr(side_k), (side_k.stride(0) if side_k is not None else 0)
+    a.dout, a.ld_dout, a.w, a.out = ptr(dout), dout.stride(0), ptr(w), ptr(out)
+    a.batch, a.heads, a.n_q, a.n_kmain = batch, heads, n_q, n_kmain
+    a.n_g, a.T, a.has_summary = (n_g, T, int(bool(has_summary))) if side_k is not None else (0, 0, 0)
+    a.prec, a.act_prec_set, a.act_prec = prec, int(act_prec is not None), act
+    a.q_batch_rows, a.ld_q = q_batch_rows, (q.stride(0) if q_batch_rows else 0)
+    with torch.cuda.device(out.device):
+        check(load().gava_attention_relevance(C.byref(a), stream_ptr(out.device)), "gava_attention_relevance")
     return out
 
 

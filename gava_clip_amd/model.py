@@ -846,6 +846,21 @@ class AttentionMaps:
         return f"AttentionMaps(mode={self.mode!r}, layer={self.layer!r}, {shapes})"
 
 
+class RelevanceMaps:
+    """What VitaCLIP.relevance_maps returns: fp32 device tensors, B clips of T frames as given.
+      patches [B, T, g, g] the relevance of the frame's patches for the target class, g = S / P; >= 0, not normalised
+      cls     [B, T]       ... of the CLS token itself; >= 1
+      logits  [B, C]       the raw logits of the forward that was differentiated
+      target  [B]          int64: the class each clip was asked about"""
+    __slots__ = ("patches", "cls", "logits", "target")
+
+    def __init__(self, patches, cls, logits, target):
+        self.patches, self.cls, self.logits, self.target = patches, cls, logits, target
+
+    def __repr__(self):
+        return "RelevanceMaps(" + ", ".join(f"{k}={tuple(getattr(self, k).shape)}" for k in self.__slots__) + ")"
+
+
 class VitaCLIP(nn.Module, _HipHost):
 
     def __init__(
@@ -1328,6 +1343,89 @@ class VitaCLIP(nn.Module, _HipHost):
         m = (maps.mean(1) if heads == "mean" else maps).view(B, T, *(() if heads == "mean" else (H,)), n_all)
         return AttentionMaps(mode, layer, m[..., 1:n1].reshape(*m.shape[:-1], g, g), m[..., 0], logits,
                              global_prompts=m[..., n1:n1 + G], local_prompts=m[..., n1 + G:n1 + G + Tm], summary=m[..., n_all - 1])
+
+    def relevance_maps(self, x, target=None, max_clips=None):
+        """Which patches and frames of the clips speak FOR a class -> RelevanceMaps (patches [B, T, g, g], cls [B, T], logits
+        [B, C], target [B]): gradient-weighted attention relevance (Chefer et al., "Generic Attention-model Explainability",
+        the self-attention rule).  It is the class-specific counterpart of attention_maps(mode="rollout"), with every block's
+        attention matrix replaced by  A-_l = mean_h max(0, grad A_l,h * A_l,h):
+          A_l,h   block l's probabilities over ALL its keys, as the forward used them (not renormalised, unlike the rollout),
+          grad    d s / d A_l,h for s = sum_b logits[b, target_b], the raw logits, as saliency() differentiates them,
+        both restricted to the frame's own tokens (CLS + patches).  The relevance of the CLS token is row 0 of
+        (I + A-_L) ... (I + A-_1), run as the vector chain r <- e_cls, r <- r + r A-_l from the last block to the first
+        inside the HIP backward of the vision tower (gava_attention_relevance, one launch per block, on the d mix the backward
+        forms anyway; neither the probabilities nor their gradients are ever in memory).
+        The result is NOT normalised: its scale is the gradient's (patches >= 0, cls >= 1, no fixed sum); compare maps of one
+        call, or normalise them yourself.  The prompt tokens are rebuilt in every block and carry no token identity between
+        blocks - the restriction the rollout documents -, so relevance that flows through the local-prompt / summary path
+        from frame to frame is NOT attributed; the gradient itself is the true one, prompt path included.
+        x: a device clip batch [B, 3, T, S, S] as forward() takes it (decoded uint8 videos: `preprocessor.batch(videos)`
+        first).  T need not be num_frames; the B*T frames must be whole num_frames groups, as for attention_maps.  target: as
+        for saliency - None (the top-1 class of this very forward, picked on the device), an int (checked on the host) or an
+        int64 [B] device tensor (not range-checked).  The clips run in chunks of whole groups whose kept activations
+        (training.kept_bytes) fit keep_activation_bytes - a chunk that still does not fit recomputes its blocks, in bf16 -;
+        max_clips sets the clips per chunk instead.  Chunking does not change a bit of the result.
+        Works in eval() and train() mode, whatever is trainable; no .grad is touched, no graph and no kept activation survives
+        the call, nothing waits for the device.  A per-descriptor (use_descriptor) head is refused, and so is a shape with more
+        keys per frame than gava_attention_relevance takes."""
+        from . import training
+        sh, Tm = self._shape, self.num_frames
+        if not (torch.is_tensor(x) and x.dim() == 5 and x.is_floating_point() and x.shape[1] == 3 and x.shape[3] == x.shape[4] == sh["size"]):
+            raise hip.GavaError(f"relevance_maps takes a floating-point clip batch [B, 3, T, {sh['size']}, {sh['size']}], got "
+                                f"{(x.dtype, tuple(x.shape)) if torch.is_tensor(x) else type(x)}")
+        if not x.is_cuda:
+            raise hip.GavaError("VitaCLIP (gava_clip_amd) runs on the HIP device only: move the model and the "
+                                "input with .cuda(); there is no CPU fallback")
+        if self.use_text_prompt_learning and self.prompt_learner.n_kv is None:
+            raise hip.GavaError("relevance_maps: a per-descriptor (use_descriptor / desc_wise) head has no single logit per class to differentiate")
+        B, T = x.shape[0], x.shape[2]
+        n_cls = self.prompt_learner.n_cls if self.use_text_prompt_learning else self.text_features.shape[0]
+        if target is not None and not torch.is_tensor(target):
+            if not 0 <= int(target) < n_cls:
+                raise hip.GavaError(f"relevance_maps: target {target} is outside the {n_cls} classes")
+        elif target is not None and not (target.is_cuda and target.dtype == torch.int64 and tuple(target.shape) == (B,)):
+            raise hip.GavaError(f"relevance_maps: a tensor target must be int64 [{B}] on the device")
+        unit = Tm // math.gcd(T, Tm)                  # the fewest clips that are whole num_frames groups
+        if B == 0 or B % unit:
+            raise hip.GavaError(f"relevance_maps: {B} clips of {T} frames are not whole groups of num_frames = {Tm}")
+        g = sh["size"] // sh["P"]
+        n1 = g * g + 1
+        n_all = n1 + sh["G"] + Tm + 1
+        if n_all > hip.ATTENTION_RELEVANCE_MAX_KEYS:
+            raise hip.GavaError(f"relevance_maps: {n_all} keys per frame, gava_attention_relevance takes at most {hip.ATTENTION_RELEVANCE_MAX_KEYS}")
+        if max_clips is None:
+            step = B // unit * unit
+            while step > unit and training.kept_bytes(self, step, T) > self.keep_activation_bytes:
+                step = (step // unit + 1) // 2 * unit
+        else:
+            step = min(B, max(int(max_clips) // unit * unit, unit))
+        rs, logits, targets = [], [], []
+        for i in range(0, B, step):
+            tg = target[i:i + step] if torch.is_tensor(target) else target
+            r, lg, tg = self._relevance_chunk(x[i:i + step], tg, {})
+            rs.append(r), logits.append(lg), targets.append(tg)
+        m = (rs[0] if len(rs) == 1 else torch.cat(rs, 0)).view(B, T, n1)
+        cat = lambda ts: ts[0] if len(ts) == 1 else torch.cat(ts, 0)
+        return RelevanceMaps(m[..., 1:].reshape(B, T, g, g), m[..., 0], cat(logits), target if torch.is_tensor(target) else cat(targets))
+
+    def _relevance_chunk(self, x, target, state):
+        """One chunk of relevance_maps: the grad-enabled forward of whole groups and the vision tower's backward with the
+        relevance request.  state: the request's state ({}; tests pass dict(capture=[]), see training._relevance_step).
+        -> (r fp32 [B*T, n1], logits [B, C], target int64 [B])."""
+        with torch.cuda.device(x.device), torch.enable_grad():
+            xg = x.detach().float().contiguous().requires_grad_()       # a leaf of this call's own: it makes the tower differentiable
+            request = dict(relevance=state)
+            logits = self._forward_impl(xg, None, None, False, input_request=request)[0]
+            if target is None:
+                target = logits.detach().argmax(dim=1)
+            elif not torch.is_tensor(target):
+                target = torch.full((x.shape[0],), int(target), dtype=torch.int64, device=x.device)
+            score = logits.gather(1, target.view(-1, 1)).sum()
+            torch.autograd.grad(score, [xg], allow_unused=True)          # runs the vision tower's backward, nothing else
+        if torch.is_tensor(self.text_features) and self.text_features.requires_grad:
+            self.text_features = self.text_features.detach()        # the last reference into this call's graph
+        state.pop("r", None)
+        return request.pop("out"), logits.detach(), target
 
     def _maps_logits(self, video):
         """The inference head (gava_similarity_head) on this rank's clip features; text features from the cache when it is

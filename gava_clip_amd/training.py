@@ -26,6 +26,8 @@ VitaCLIP_vision_encoder_utils.py:155-203 in reverse as a list of stages, on scra
     _embedding_backward  ln_pre', sum over tokens = d time_embed
     _input_backward      only when d x is asked for: patch projection^T (dgrad GEMM), then the fold of the patch rows back into
                          the clip (gava_unpatchify) - the gradient itself, or a saliency map of it without the gradient in memory
+    _relevance_step      only with a relevance request (VitaCLIP.relevance_maps): per block, right after its d mix exists, one step of
+                         the gradient-weighted attention relevance chain (gava_attention_relevance); the backward ends after block 0's
 The second half of the module is the step's tail: similarity head and criterion on the device.
 """
 import ctypes as C
@@ -102,11 +104,14 @@ def _mlp_backward(P, ln2_g, dX, s, X1, pre, act):
     hip.gemm(s.dx16, P["w_out_t"], None, s.dmix, epilogue=hip.EPI_H16, prec=BWD)
 
 
-def _block_backward(P, ln2_g, dX, s, X1, pre, qkv, act, **attn):
+def _block_backward(P, ln2_g, dX, s, X1, pre, qkv, act, rel=None, **attn):
     """MLP' and attention' of a block on all its rows; s.dxn is left holding the input of LN1' for the caller.  Attention
     branch: x1 = x0 + out_proj(attn(in_proj(ln_1 x0))) (VitaCLIP_text_encoder.py:81-85; vision_encoder_utils.py:61-81,190-191);
-    `attn` are the tower's keyword arguments of hip.attention_backward."""
+    `attn` are the tower's keyword arguments of hip.attention_backward.  rel (vision, relevance request only): called with the
+    block's queries and s.dmix as soon as that exists; a true result (-> True) ends the block there."""
     _mlp_backward(P, ln2_g, dX, s, X1, pre, act)
+    if rel is not None and rel(split3(qkv)[0], s.dmix):
+        return True
     hip.attention_backward(*split3(qkv), s.dmix, *split3(s.dqkv), prec=BWD, q_scale=0.125, act_prec=act, **attn)
     hip.gemm(s.dqkv, P["w_qkv_t"], None, s.dxn, epilogue=hip.EPI_F32, prec=BWD)
 
@@ -341,17 +346,19 @@ def _main_activations(kept, i, cls_only, P, prm, X0, SIDE, d, s):
     return s.SIDEKV, s.qkv, s.X1, s.pre
 
 
-def _cls_only_backward(P, ln2_g, dX, s, last_q, qkv, X1c, pre_c, act, **attn):
+def _cls_only_backward(P, ln2_g, dX, s, last_q, qkv, X1c, pre_c, act, rel=None, **attn):
     """The main-row backward of a kept last block: only the CLS rows carry a gradient (VitaCLIP_vision_encoder.py:126) -
     MLP', out_proj' and the query side of attention' on B*T rows (last_q, X1c, pre_c: the CLS rows' queries, stream and
     pre-activation); keys / values (and through them every row of the block input) in full.  Leaves s.dxn like
-    `_block_backward`."""
+    `_block_backward`, and takes `rel` like it (the queries and d mix are then the CLS rows' own buffers)."""
     BT, D = last_q.shape
     n1 = dX.shape[0] // BT
     c = _block_scratch(dX.device, BT, D, pre_c.shape[1])
     dXc = dX.view(BT, n1, D)[:, 0].contiguous()
     hip.convert_h16(dXc, BWD, out=c.dx16)
     _mlp_backward(P, ln2_g, dXc, c, X1c, pre_c, act)
+    if rel is not None and rel(last_q, c.dmix):
+        return True
     dq_c = new(dX.device, BT, D)
     hip.attention_backward(last_q, *split3(qkv)[1:], c.dmix, dq_c, *split3(s.dqkv)[1:], prec=BWD, q_scale=0.125, act_prec=act,
                            n_q=1, q_batch_rows=1, **attn)
@@ -359,6 +366,29 @@ def _cls_only_backward(P, ln2_g, dX, s, last_q, qkv, X1c, pre_c, act, **attn):
     dxn_cls = s.dxn.view(BT, n1 * D)[:, :D]                                                     # CLS rows, stride n1*D
     hip.gemm(dq_c, P["w_qkv_t"][:, :D], None, dxn_cls, epilogue=hip.EPI_F32, prec=BWD, resid=dxn_cls)   # + dQ . Wq
     dX.view(BT, n1, D)[:, 0] = dXc
+
+
+def _relevance_step(st, d, i, q, qkv, SIDEKV, dmix, act):
+    """One step of the relevance chain (VitaCLIP.relevance_maps) at block i, from the last block to the
+    first: r <- r + mean_h gava_attention_relevance(w = r) on this block's q / k / v, the prompt rows' keys and d mix, the
+    gradient with respect to the attention output that the backward has just formed.  In the last block only the CLS rows
+    of d mix are non-zero (only the CLS output is used), so its step is the one-query form r = e_cls + mean_h out, whether
+    q and dmix are the CLS rows' own buffers (kept route) or the block's full ones (recompute route).  st: the request's
+    state - "r" fp32 [BT, n1]; "capture" (tests only): a list that receives clones of the step's operands.  -> True after
+    block 0's step: the chain is complete and nothing further of the backward is needed."""
+    D = d.D
+    k, v, side_k = qkv[:, D:2 * D], qkv[:, 2 * D:], SIDEKV[:, :D]
+    if st.get("capture") is not None:
+        c = lambda t: t.clone(memory_format=torch.contiguous_format)
+        st["capture"].append(dict(layer=i, q=c(q), k=c(k), v=c(v), side_k=c(side_k), dmix=c(dmix), act=act))
+    common = dict(batch=d.BT, heads=d.H, n_kmain=d.n1, prec=BWD, act_prec=act, side_k=side_k, n_g=d.G, T=d.T, has_summary=True)
+    if i == d.NL - 1:
+        r = hip.attention_relevance(q, k, v, dmix, n_q=1, q_batch_rows=q.shape[0] // d.BT, **common).mean(1)
+        r[:, 0] += 1.0
+    else:
+        r = st["r"] + hip.attention_relevance(q, k, v, dmix, n_q=d.n1, w=st["r"], **common).mean(1)
+    st["r"] = r.contiguous()
+    return i == 0
 
 
 def _prompt_backward(P, prm, i, SIDE, dsummary, dX, grads, dgp, d, s):
@@ -432,7 +462,10 @@ def vision_backward(model, saved, dcls_x, B, T, dsummary=None, kept=None, input_
     activations are then in the forward's operand type (fp16 by default) while gradients stay bf16 - the attention
     backward converts K/V/Q as it stages them, the QuickGELU' epilogue decodes the pre-activation by its own flag.
     input_grad: None, or dict(mode=hip.UNPATCH_*, x=the fp32 clip or None) - the result then also holds "input", the gradient
-    with respect to the clip or the saliency map of it (_input_backward); without it not one launch differs."""
+    with respect to the clip or the saliency map of it (_input_backward); without it not one launch differs.  Or
+    dict(relevance=state): every block also runs _relevance_step, the gradient chain between the blocks stays the true one
+    (prompt path included), and the call ends after block 0's step - what follows it (attention', the prompt path, LN1', the
+    embedding, the input) adds nothing to the chain - with {"relevance": r fp32 [B*T, n1]} as its only result."""
     bw, v = model._backward_pack("vision"), model.visual
     d = _vision_dims(model, B, T, dcls_x.device)
     if kept is not None:      # block inputs x[i] (x[NL]: the last block's output), embedding output, activations' storage type
@@ -444,6 +477,7 @@ def vision_backward(model, saved, dcls_x, B, T, dsummary=None, kept=None, input_
     s = _vision_scratch(d, recompute=kept is None)
     hip.convert_h16(dX, BWD, out=s.dx16)
     dgp = torch.zeros_like(v.global_prompts, dtype=torch.float32)
+    rel_state = input_grad.get("relevance") if input_grad is not None else None
     for i in reversed(range(NL)):
         P, blk, X0 = bw["layers"][i], v.blocks[i], xs[i]
         prm = _block_params(blk)
@@ -452,10 +486,15 @@ def vision_backward(model, saved, dcls_x, B, T, dsummary=None, kept=None, input_
         SIDEKV, qkv, X1, pre = _main_activations(kept, i, cls_only, P, prm, X0, SIDE, d, s)
         attn = dict(batch=d.BT, heads=d.H, n=d.n1, side_k=SIDEKV[:, :D], side_v=SIDEKV[:, D:], dside_k=s.part[:, :D],
                     dside_v=s.part[:, D:], n_g=d.G, T=d.T, has_summary=True)
+        rel = None
+        if rel_state is not None:
+            rel = lambda q, dmix, i=i, qkv=qkv, SIDEKV=SIDEKV: _relevance_step(rel_state, d, i, q, qkv, SIDEKV, dmix, act)
         if cls_only:
-            _cls_only_backward(P, prm.ln[2], dX, s, last_q, qkv, X1, pre, act, **attn)
+            done = _cls_only_backward(P, prm.ln[2], dX, s, last_q, qkv, X1, pre, act, rel=rel, **attn)
         else:
-            _block_backward(P, prm.ln[2], dX, s, X1, pre, qkv, act, **attn)
+            done = _block_backward(P, prm.ln[2], dX, s, X1, pre, qkv, act, rel=rel, **attn)
+        if done:
+            return {"relevance": rel_state["r"]}
         _prompt_backward(P, prm, i, SIDE, dsummary if i == NL - 1 else None, dX, grads, dgp, d, s)
         # norm1' of the main rows is applied at the end of the block, after the prompt path has added its share to
         # the CLS rows of dX: it also writes the bf16 copy of the finished dX for the next block
@@ -476,7 +515,9 @@ class VisionTowerFn(torch.autograd.Function):
     descriptors nor the decoded videos are held for the backward.
     The backward returns d x when an fp32 x asks for it (never on the uint8 route).  request: None, or the dict of
     VitaCLIP.saliency - mode (hip.UNPATCH_*) and x; a map mode's result is left in request["out"] instead of being returned
-    (it has not x's shape), so that the full-size gradient is never formed."""
+    (it has not x's shape), so that the full-size gradient is never formed.  Or the dict of VitaCLIP.relevance_maps,
+    dict(relevance=state): the backward then runs the relevance chain beside the gradient, leaves r in request["out"] and
+    returns no gradient at all."""
 
     @staticmethod
     def forward(fctx, model, x, clips, request, *params):
@@ -508,6 +549,8 @@ class VisionTowerFn(torch.autograd.Function):
         g = vision_backward(model, saved, dcls_x.contiguous(), *fctx.BT, dsummary=dsummary, kept=kept, input_grad=req)
         fctx.kept = fctx.request = None      # release the activation buffers with the graph
         dx = g.get("input")
+        if "relevance" in g:
+            req["out"] = g["relevance"]
         if dx is not None and req["mode"] != hip.UNPATCH_GRAD:
             req["out"], dx = dx, None
         out = []

@@ -846,6 +846,52 @@ int gava_attention_mass(const gava_attention_mass_args* a, gava_stream_t stream)
 /* sizeof of gava_attention_mass_args, like gava_input_grad_struct_sizes.  Writes min(cap, 1) entries, returns 1. */
 int gava_attention_maps_struct_sizes(size_t* out, int cap);
 
+/* ---- relevance maps: one step of gradient-weighted attention relevance ------------------------------------------------------
+ *
+ * The class-specific counterpart of the rollout step above (Chefer et al., "Generic Attention-model Explainability", the
+ * self-attention rule): the block's probabilities times their gradient, clamped at zero, summed over the queries with a weight.
+ * Neither the probabilities nor their gradients exist in memory; both are formed here from what the forward kept and from the
+ * backward's gradient of the attention output.  Operands are addressed as by gava_attention_mass and gava_attention_backward:
+ * problem (f, h) = frame f, head h (columns [64h, 64h + 64)); q is h16 and already carries the 1/sqrt(64) factor; queries are
+ * rows f*q_batch_rows + [0, n_q) of q (row stride ld_q) and of dout (row stride ld_dout) - defaults, when 0: q_batch_rows = n_q,
+ * ld_q = ld_qkv; keys and values are the n_kmain rows f*n_kmain + [0, n_kmain) of k / v; the side rows [n_g global | T local of
+ * the frame's clip | summary] of side_k, in gava_attention's layout, are further KEYS of the softmax (n_g = T = has_summary =
+ * 0: none) - their values are not needed, because only the frame's own columns are written.  dout is the gradient of the
+ * scalar being explained with respect to the attention output (the input of out_proj), h16 of `prec`.  With
+ *   P[i][j] = softmax_j(q_i . k_j) over all n_kmain + n_side keys           (no renormalisation: what the forward used)
+ *   G[i][j] = sum_c dout[i][64h + c] * v[j][64h + c]                        (= d s / d P_h[i][j])
+ *   out[f][h][j] = sum_{i < n_q} w[f][i] * max(0, P[i][j] * G[i][j])        j in [0, n_kmain)
+ * w: fp32 [batch][n_q], NULL = every weight 1 (the same bits as an array of ones); the clamp is applied before the weight.
+ * out: fp32 [batch][heads][n_kmain].  n_q = 1 with w = NULL is the step of a block whose CLS row alone carries a gradient
+ * (the last one; on a kept last block q and dout are [batch][D] buffers of their own: q_batch_rows = 1); n_q = n_kmain with
+ * w = r is the chain step r <- r + mean_h(out) of every other block.
+ * prec is dout's type; act_prec_set / act_prec have gava_attention_backward's meaning: q / k / v / side_k are stored as
+ * act_prec (fp16 activations kept from the forward) while dout is prec (bf16); 0 = same as prec.  The scores are products of
+ * the STORED q and k (the forward's probabilities); v is converted to prec as it is loaded, as the backward does, and G is a
+ * product in prec.  MFMA products accumulated in fp32, fp32 softmax in exp2 form, nothing is rounded to 16 bits after the
+ * MFMAs.  Every output element is summed by one wave in a fixed order (queries ascending per lane, then a fixed butterfly over
+ * sixteen lanes): no atomics, two runs give the same bits.  One launch on `stream`.
+ * Limits: K of one (frame, head) is resident in LDS, so n_kmain + n_side <= 640; n_q <= n_kmain.  GAVA_EINVAL, before any
+ * launch: beyond those limits, null args / q / k / v / dout / out, batch, heads, n_q or n_kmain < 1, ld_qkv / ld_side /
+ * ld_dout / ld_q not a multiple of 8 or below heads*64, q / k / v / dout / side_k not 16-byte aligned, w / out not 4-byte
+ * aligned, side rows asked for without side_k or with batch % T != 0, q_batch_rows < n_q, an unknown prec or act_prec or a
+ * pair other than (f16, f16), (bf16, bf16), (prec bf16, act_prec f16). */
+typedef struct {
+  const void* q; const void* k; const void* v; int64_t ld_qkv;     /* h16 of act_prec, element strides */
+  const void* side_k; int64_t ld_side;
+  const void* dout; int64_t ld_dout;                               /* h16 of prec */
+  const float* w;                                                  /* fp32 [batch][n_q] or NULL */
+  float* out;                                                      /* fp32 [batch][heads][n_kmain] */
+  int batch, heads, n_q, n_kmain;
+  int n_g, T, has_summary;
+  int prec, act_prec_set, act_prec;
+  int q_batch_rows, reserved; int64_t ld_q;
+} gava_attention_relevance_args;
+int gava_attention_relevance(const gava_attention_relevance_args* a, gava_stream_t stream);
+
+/* sizeof of gava_attention_relevance_args, like gava_attention_maps_struct_sizes.  Writes min(cap, 1) entries, returns 1. */
+int gava_attention_relevance_struct_sizes(size_t* out, int cap);
+
 /* sizeof of every ABI struct as the library was compiled, in the order gemm_args, layernorm_args, attention_args,
  * attention_f32_args, clip_desc, vision_layer, vision_layer8, vision_model, text_layer, text_model, layernorm_bwd_args,
  * attention_bwd_args, vision_saved, preprocess_args, patchify_args, preprocess_clips_args, view_scores_args.  Writes
