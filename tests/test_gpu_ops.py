@@ -12,6 +12,7 @@ from gava_clip_amd import hip  # noqa: E402
 
 PRECS = [hip.PREC_F16, hip.PREC_BF16]
 EPS16 = {hip.PREC_F16: 2 ** -11, hip.PREC_BF16: 2 ** -8}
+EIGHT_WORKGROUPS = 1 << 20     # gava_gemm_args.cu_reserve: any reserve >= CUs - 8 leaves a persistent launch 8 workgroups, on any device
 
 
 def dev():
@@ -248,7 +249,10 @@ def test_split_precision_chain(prec, tol):
 
 @pytest.mark.parametrize("prec", PRECS)
 def test_gemm_large_m_patch_split_and_ragged(prec):
-    """The persistent 256x256 kernel (M > 2048, N % 256 == 0): patch epilogue, split output, rows >= M."""
+    """M > 2048 with N = 256, K = 192: patch epilogue, split output, rows >= M.  With today's launch_prec both shapes (3200 x 256
+    x 192 patch, 2600 x 256 x 192 split) go to the 128^2 tile kernel with the two-stage ring, launch_tile<128, 128, 2>: N < 1536,
+    K < 2048 and fewer than 512 tiles of 256^2.  The persistent 256^2 kernel's SPLIT and EPI_F32_PATCH instantiations are
+    launched by name in test_gpu_gemm_edges.py."""
     d = dev()
     dt = hip.h16_dtype(prec)
     frames, n, T, D, K = 200, 16, 4, 256, 192
@@ -660,8 +664,12 @@ def _a8_rows(a16, pitch):
     return buf
 
 
-@pytest.mark.parametrize("M,N,K,kind", [(45056, 768, 3072, "fc2"), (20000, 2304, 768, "qkv"), (300, 3072, 768, "fc1"), (5000, 768, 768, "fc2")])
-def test_gemm_weight_lo_pass_at_8_bits(M, N, K, kind):
+# (the last one: the kernel's minimum K = 128, one 8-bit stage per tile, on 8 workgroups - 16 tiles, two per workgroup, so that the
+# tile switch inside the 8-bit loop runs at nk8 = 1)
+@pytest.mark.parametrize("M,N,K,kind,cu_reserve", [(45056, 768, 3072, "fc2", 0), (20000, 2304, 768, "qkv", 0), (300, 3072, 768, "fc1", 0),
+                                                   (5000, 768, 768, "fc2", 0), (3900, 256, 128, "fc2", EIGHT_WORKGROUPS)],
+                         ids=["45056-768-3072-fc2", "20000-2304-768-qkv", "300-3072-768-fc1", "5000-768-768-fc2", "3900-256-128-fc2-wg8"])
+def test_gemm_weight_lo_pass_at_8_bits(M, N, K, kind, cu_reserve):
     """gava_gemm_args.w_lo = 2: after the K-deep fp16 loop the persistent kernel runs K / 128 stages of
     v_mfma_scale_f32_16x16x128_f8f6f4 on A8 = bf8(A) and W8 = e4m3(2^e (W - W_hi)) into the same accumulators.  Checked
     against exactly that arithmetic on the host (A16 . W_hi^T + A8 . W8^T 2^-e in fp64), then against A16 . W^T (the point of
@@ -684,7 +692,7 @@ def test_gemm_weight_lo_pass_at_8_bits(M, N, K, kind):
         x8 = torch.zeros(Mp, 2 * N, dtype=torch.uint8, device=d)
         part = torch.zeros(Mp + 32, 4, 2, dtype=torch.float32, device=d)
         hip.gemm(A, hl, bias, X, epilogue=hip.EPI_F32, prec=prec, resid=X, w_lo=2, K=K, A8=A8, W8=w8, w8_exp=e8,
-                 x16_out=x16, rowsum_out=part, rowsum_reduced=True, x8_out=x8)
+                 x16_out=x16, rowsum_out=part, rowsum_reduced=True, x8_out=x8, cu_reserve=cu_reserve)
         want = X0.double() + A.double() @ hi.double().t() + _bf8(A).float().double().to(d) @ w8deq.t() + bias.double()
         assert torch.allclose(X.double(), want, rtol=2e-5, atol=2e-5)
         exact = X0.double() + A.double() @ Wf.double().t() + bias.double()
@@ -720,7 +728,7 @@ def test_gemm_weight_lo_pass_at_8_bits(M, N, K, kind):
     for kw in (dict(fold_stats=stats), dict(fold_partials=part)):
         out = torch.zeros(M, N, dtype=dt, device=d)
         out8 = torch.zeros(M, 2 * N, dtype=torch.uint8, device=d)
-        hip.gemm(x16, hl, None, out, epilogue=epi, prec=prec, fold_s=s8, fold_t=ft, w_lo=2, K=K, A8=A8, W8=w8, w8_exp=e8, out8=out8, **kw)
+        hip.gemm(x16, hl, None, out, epilogue=epi, prec=prec, fold_s=s8, fold_t=ft, w_lo=2, K=K, A8=A8, W8=w8, w8_exp=e8, out8=out8, cu_reserve=cu_reserve, **kw)
         assert torch.allclose(out.float(), want, rtol=tol, atol=2 * tol), list(kw)
         got8 = out8[:, :N].cpu().view(torch.float8_e5m2).float()
         assert torch.allclose(got8, out.float().cpu(), rtol=0.13, atol=1e-4)      # bf8: 2 mantissa bits
@@ -770,8 +778,10 @@ def test_gemm_ping_pong_kernel(prec, M, N, K):
 
 
 @pytest.mark.parametrize("prec", PRECS)
-@pytest.mark.parametrize("M,D", [(45000, 768), (300, 768), (20000, 1024), (100864, 768)])
-def test_gemm_residual_stream_as_16_bit_pair(prec, M, D):
+# (the last one: the form's minimum K = 256 (and 1024) on 8 workgroups - 24 tiles, three per workgroup through the tile switch)
+@pytest.mark.parametrize("M,D,cu_reserve", [(45000, 768, 0), (300, 768, 0), (20000, 1024, 0), (100864, 768, 0), (6000, 256, EIGHT_WORKGROUPS)],
+                         ids=["45000-768", "300-768", "20000-1024", "100864-768", "6000-256-wg8"])
+def test_gemm_residual_stream_as_16_bit_pair(prec, M, D, cu_reserve):
     """gava_gemm_args.resid16 (gemm256_kernel<..., HL>): the residual producers reading and writing the stream as hi = h16(x),
     lo = fp16(x - hi).  Against the fp32-stream kernel on the same inputs (resid = hi + lo, exact in fp32): the hi half is its
     x16 copy bit for bit (same k order, same fp32 x), the row sums are its row sums to fp32 rounding, hi + lo is its fp32 output to 2^-21 |x|
@@ -792,12 +802,12 @@ def test_gemm_residual_stream_as_16_bit_pair(prec, M, D):
         Y = torch.zeros(M, D, device=d)
         x16 = torch.zeros(Mp, D, dtype=dt, device=d)
         part = torch.zeros(Mp + 32, 4, 2, dtype=torch.float32, device=d)
-        hip.gemm(A, W, b, Y, epilogue=hip.EPI_F32, prec=prec, resid=Xp, x16_out=x16, rowsum_out=part, rowsum_reduced=True, kernel=hip.KERNEL_PP)
+        hip.gemm(A, W, b, Y, epilogue=hip.EPI_F32, prec=prec, resid=Xp, x16_out=x16, rowsum_out=part, rowsum_reduced=True, kernel=hip.KERNEL_PP, cu_reserve=cu_reserve)
         hi = torch.full((Mp + 8, D), 7.0, dtype=dt, device=d)
         lo = torch.full((Mp + 8, D), 7.0, dtype=torch.float16, device=d)
         part2 = torch.zeros(Mp + 32, 4, 2, dtype=torch.float32, device=d)
         hip.gemm(A, W, b, None, epilogue=hip.EPI_F32, prec=prec, resid16=hi0, resid_lo=lo0, x16_out=hi, xlo_out=lo, rowsum_out=part2,
-                 rowsum_reduced=True)
+                 rowsum_reduced=True, cu_reserve=cu_reserve)
         assert torch.equal(hi[:M], x16[:M]), K
         # (a lane adds its 16 columns in another order than the fp32-output layout's lane does: equal to fp32 rounding, not bit for bit)
         assert torch.allclose(part2[:M, :D // 256], part[:M, :D // 256], rtol=2e-6, atol=1e-4), K
@@ -811,7 +821,7 @@ def test_gemm_residual_stream_as_16_bit_pair(prec, M, D):
         if hi_ip.shape[0] < Mp:
             hi_ip = torch.cat([hi_ip, torch.zeros(Mp - M, D, dtype=dt, device=d)]); lo_ip = torch.cat([lo_ip, torch.zeros(Mp - M, D, dtype=torch.float16, device=d)])
         hip.gemm(A, W, b, None, epilogue=hip.EPI_F32, prec=prec, resid16=hi_ip, resid_lo=lo_ip, x16_out=hi_ip, xlo_out=lo_ip, rowsum_out=part2,
-                 rowsum_reduced=True, M=M)
+                 rowsum_reduced=True, M=M, cu_reserve=cu_reserve)
         assert torch.equal(hi_ip[:M], hi[:M]) and torch.equal(lo_ip[:M], lo[:M]), K
     # weight-lo pass (w_lo = 1) with the pair: against the fp32-stream kernel with the same packed weight
     K = D
@@ -819,8 +829,8 @@ def test_gemm_residual_stream_as_16_bit_pair(prec, M, D):
     Wf = rnd((D, K), K ** -0.5, 2).to(d)
     Wh = Wf.to(dt)
     Wp = torch.cat([Wh, (Wf - Wh.float()).to(dt)], 1).contiguous()
-    hip.gemm(A, Wp, b, Y, epilogue=hip.EPI_F32, prec=prec, resid=Xp, x16_out=x16, rowsum_out=part, rowsum_reduced=True, kernel=hip.KERNEL_PP, w_lo=1)
-    hip.gemm(A, Wp, b, None, epilogue=hip.EPI_F32, prec=prec, resid16=hi0, resid_lo=lo0, x16_out=hi, xlo_out=lo, rowsum_out=part2, rowsum_reduced=True, w_lo=1)
+    hip.gemm(A, Wp, b, Y, epilogue=hip.EPI_F32, prec=prec, resid=Xp, x16_out=x16, rowsum_out=part, rowsum_reduced=True, kernel=hip.KERNEL_PP, w_lo=1, cu_reserve=cu_reserve)
+    hip.gemm(A, Wp, b, None, epilogue=hip.EPI_F32, prec=prec, resid16=hi0, resid_lo=lo0, x16_out=hi, xlo_out=lo, rowsum_out=part2, rowsum_reduced=True, w_lo=1, cu_reserve=cu_reserve)
     assert torch.equal(hi[:M], x16[:M]) and torch.allclose(part2[:M, :D // 256], part[:M, :D // 256], rtol=2e-6, atol=1e-4)
     # rejected: an fp32 output or residual beside the pair, a missing half, a kernel that does not implement it, K % 128
     kw = dict(epilogue=hip.EPI_F32, prec=prec, rowsum_out=part2, rowsum_reduced=True)
