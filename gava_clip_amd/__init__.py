@@ -13,6 +13,9 @@ def __getattr__(name):  # lazy: importing the package must not need torch/HIP
     if name == "RelevanceMaps":
         from .model import RelevanceMaps
         return RelevanceMaps
+    if name in ("PerturbationCurves", "Faithfulness"):
+        from . import model
+        return getattr(model, name)
     if name == "TrainCriterion":
         from .training import TrainCriterion
         return TrainCriterion

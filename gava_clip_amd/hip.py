@@ -36,9 +36,18 @@ EXPORTS = ["gava_abi_version", "gava_gemm", "gava_layernorm", "gava_attention",
            "gava_adamw_plan", "gava_adamw_step", "gava_optim_struct_sizes",
            "gava_unpatchify", "gava_input_grad_struct_sizes",
            "gava_attention_mass", "gava_attention_maps_struct_sizes",
-           "gava_attention_relevance", "gava_attention_relevance_struct_sizes"]
+           "gava_attention_relevance", "gava_attention_relevance_struct_sizes",
+           "gava_patch_ranks", "gava_blur_clips", "gava_perturb_clips", "gava_perturb_scores", "gava_perturbation_struct_sizes"]
 ATTENTION_MASS_MAX_KEYS = 640     # gava_attention_mass keeps K of one (frame, head) resident in LDS
 ATTENTION_RELEVANCE_MAX_KEYS = 640     # and so does gava_attention_relevance
+PERTURB_MAX_UNITS = 65536         # patches or frames one gava_patch_ranks ranking holds
+PERTURB_MAX_STEPS = 128           # thresholds / fractions gava_perturb_clips and gava_perturb_scores take by value
+BLUR_MAX_RADIUS = 64
+RANK_PATCH, RANK_PIXEL, RANK_FRAME = 0, 1, 2
+SCOPE_CLIP, SCOPE_FRAME = 0, 1
+UNITS_PATCH, UNITS_FRAME = 0, 1
+PERTURB_DELETION, PERTURB_INSERTION = 0, 1
+BASELINE_ZERO, BASELINE_CHANNEL, BASELINE_TENSOR = 0, 1, 2
 ADAMW_MAX_GROUPS = 8
 
 _vp, _fp, _ip = C.c_void_p, C.c_void_p, C.c_void_p  # all device pointers travel as void*
@@ -247,6 +256,29 @@ class AttentionRelevanceArgs(C.Structure):
                 ("q_batch_rows", C.c_int), ("reserved", C.c_int), ("ld_q", C.c_int64)]
 
 
+class PatchRanksArgs(C.Structure):
+    _fields_ = [("scores", _fp), ("ranks", _ip), ("pooled", _fp),
+                ("B", C.c_int), ("T", C.c_int), ("g", C.c_int), ("patch", C.c_int), ("layout", C.c_int), ("scope", C.c_int)]
+
+
+class BlurClipsArgs(C.Structure):
+    _fields_ = [("x", _fp), ("taps", _fp), ("tmp", _fp), ("out", _fp),
+                ("B", C.c_int), ("T", C.c_int), ("size", C.c_int), ("radius", C.c_int)]
+
+
+class PerturbClipsArgs(C.Structure):
+    _fields_ = [("x", _fp), ("ranks", _ip), ("baseline", _fp), ("out", _fp),
+                ("nb", C.c_int), ("T", C.c_int), ("size", C.c_int), ("patch", C.c_int), ("units", C.c_int), ("mode", C.c_int),
+                ("baseline_kind", C.c_int), ("n_steps", C.c_int), ("k", C.c_int * PERTURB_MAX_STEPS)]
+
+
+class PerturbScoresArgs(C.Structure):
+    _fields_ = [("logits", _fp), ("ld", C.c_int64), ("target", _ip), ("logit", _fp), ("prob", _fp), ("top1", _ip),
+                ("auc_logit", _fp), ("auc_prob", _fp), ("target_out", _ip),
+                ("nb", C.c_int), ("n_steps", C.c_int), ("C", C.c_int), ("ref_step", C.c_int),
+                ("fractions", C.c_float * PERTURB_MAX_STEPS)]
+
+
 class VisionSaved(C.Structure):
     _fields_ = [("e0", _fp), ("x", _fp), ("x1", _fp), ("qkv", _vp), ("pre", _vp), ("sidekv", _vp),
                 ("last_q", _vp), ("last_x1", _fp), ("last_pre", _vp)]
@@ -438,6 +470,18 @@ def load():
     if lib.gava_attention_relevance_struct_sizes(sizes, len(relevance_mirrors)) != len(relevance_mirrors):
         raise GavaError("libgava_hip.so and gava_clip_amd/hip.py disagree on the number of relevance ABI structs")
     for cls, sz in zip(relevance_mirrors, sizes):
+        if C.sizeof(cls) != sz:
+            raise GavaError(f"ctypes mirror {cls.__name__} is {C.sizeof(cls)} bytes, the library's struct {sz}: gava_clip_amd/hip.py is out of "
+                            f"step with include/gava_hip.h")
+    # the faithfulness curves' structs, the same way
+    perturbation_mirrors = [PatchRanksArgs, BlurClipsArgs, PerturbClipsArgs, PerturbScoresArgs]
+    for name, cls in (("gava_patch_ranks", PatchRanksArgs), ("gava_blur_clips", BlurClipsArgs),
+                      ("gava_perturb_clips", PerturbClipsArgs), ("gava_perturb_scores", PerturbScoresArgs)):
+        getattr(lib, name).argtypes, getattr(lib, name).restype = [C.POINTER(cls), _vp], C.c_int
+    lib.gava_perturbation_struct_sizes.argtypes, lib.gava_perturbation_struct_sizes.restype = [C.POINTER(C.c_size_t), C.c_int], C.c_int
+    if lib.gava_perturbation_struct_sizes(sizes, len(perturbation_mirrors)) != len(perturbation_mirrors):
+        raise GavaError("libgava_hip.so and gava_clip_amd/hip.py disagree on the number of perturbation ABI structs")
+    for cls, sz in zip(perturbation_mirrors, sizes):
         if C.sizeof(cls) != sz:
             raise GavaError(f"ctypes mirror {cls.__name__} is {C.sizeof(cls)} bytes, the library's struct {sz}: gava_clip_amd/hip.py is out of "
                             f"step with include/gava_hip.h")
@@ -728,6 +772,200 @@ def attention_relevance(q, k, v, dout, out=None, *, batch, heads, n_q, n_kmain, 
     with torch.cuda.device(out.device):
         check(load().gava_attention_relevance(C.byref(a), stream_ptr(out.device)), "gava_attention_relevance")
     return out
+
+
+# ---- faithfulness curves (gava_patch_ranks, gava_blur_clips, gava_perturb_clips, gava_perturb_scores) ---------------------------
+# Every wrapper checks shapes and dtypes first and the device last, so that a wrong call is refused with the same words with or
+# without a GPU; nothing reaches the library before all of it passed.
+
+def _is_f32(t):
+    return torch.is_tensor(t) and t.dtype == torch.float32 and t.is_contiguous()
+
+
+def _on_device(what, *tensors):
+    ts = [t for t in tensors if t is not None]
+    _require(all(t.is_cuda for t in ts), f"{what}: every tensor must be on the HIP device: there is no CPU fallback")
+    _require(all(t.device == ts[0].device for t in ts), f"{what}: tensors on different devices")
+
+
+def perturb_thresholds(n, steps=10, fractions=None):
+    """The abscissae of a perturbation curve and its thresholds: fractions (default linspace(0, 1, steps + 1); a given list must
+    start at 0, end at 1 and increase strictly) -> (fractions as a list of floats, k) with k_s = floor(f_s * n + 0.5) in float64,
+    n = units per ranking.  Host arithmetic only."""
+    import math
+    _require(isinstance(n, int) and n >= 1, f"perturb_thresholds: {n!r} units per ranking")
+    if fractions is None:
+        _require(isinstance(steps, int) and not isinstance(steps, bool) and steps >= 1, f"perturb_thresholds: steps must be an int >= 1, got {steps!r}")
+        f = [s / steps for s in range(steps + 1)]
+    else:
+        try:
+            f = [float(v) for v in (fractions.tolist() if torch.is_tensor(fractions) else fractions)]
+        except (TypeError, ValueError):
+            raise GavaError(f"perturb_thresholds: fractions must be a list of numbers, got {fractions!r}") from None
+        _require(len(f) >= 2 and f[0] == 0.0 and f[-1] == 1.0, f"perturb_thresholds: fractions must start at 0 and end at 1, got {f}")
+        _require(all(math.isfinite(v) for v in f) and all(b > a for a, b in zip(f, f[1:])),
+                 f"perturb_thresholds: fractions must increase strictly, got {f}")
+    _require(len(f) <= PERTURB_MAX_STEPS, f"perturb_thresholds: {len(f)} fractions, at most {PERTURB_MAX_STEPS} are supported")
+    return f, [int(math.floor(v * n + 0.5)) for v in f]
+
+
+def gaussian_taps(sigma):
+    """The blur's taps: exp(-i^2 / 2 sigma^2) for |i| <= r = ceil(3 sigma), normalised in float64, then rounded to fp32 (host)."""
+    import math
+    _require(isinstance(sigma, (int, float)) and math.isfinite(sigma) and sigma > 0, f"gaussian_taps: sigma must be a positive number, got {sigma!r}")
+    r = int(math.ceil(3.0 * sigma))
+    _require(r <= BLUR_MAX_RADIUS, f"gaussian_taps: sigma {sigma} needs radius {r}, at most {BLUR_MAX_RADIUS} is supported")
+    w = torch.exp(-torch.arange(-r, r + 1, dtype=torch.float64) ** 2 / (2.0 * float(sigma) ** 2))
+    return (w / w.sum()).float()
+
+
+def patch_ranks(scores, *, patch=None, scope="clip"):
+    """Rank the units of a score map (gava_patch_ranks).  scores fp32: [B, T, g, g] (patch=None: the unit is a patch),
+    [B, T, S, S] with patch=P (pixels, pooled to (S/P)^2 patches by the fp32 sum over each P x P patch) or [B, T] (the unit is a
+    frame).  scope "clip": one ranking per clip; "frame": one per frame (patch units only).  -> int32 [B, T*g*g] or [B, T],
+    rank 0 = the most important unit: descending by value, -0 == +0, ties to the lower index, NaNs after -inf.  At most
+    PERTURB_MAX_UNITS units per ranking.  One launch (pixels: two, through a [B, T, g, g] workspace allocated here), no sync."""
+    _require(scope in ("clip", "frame"), f"patch_ranks: scope must be 'clip' or 'frame', got {scope!r}")
+    _require(_is_f32(scores) and scores.dim() in (2, 4), "patch_ranks: scores must be a contiguous fp32 [B, T, g, g], [B, T, S, S] or [B, T] tensor")
+    _require(scores.numel() > 0, f"patch_ranks: scores {tuple(scores.shape)} hold nothing")
+    B, T = scores.shape[:2]
+    a = PatchRanksArgs()
+    if scores.dim() == 2:
+        _require(scope == "clip", "patch_ranks: scope='frame' ranks the patches of a frame; frame scores have one unit per frame")
+        _require(patch is None, "patch_ranks: patch goes with the pixel layout [B, T, S, S]")
+        a.layout, a.g, a.patch, n, total = RANK_FRAME, 1, 0, T, T
+    else:
+        S = scores.shape[2]
+        _require(scores.shape[3] == S, f"patch_ranks: scores {tuple(scores.shape)} are not square maps")
+        if patch is None:
+            a.layout, a.g, a.patch = RANK_PATCH, S, 0
+        else:
+            _require(isinstance(patch, int) and patch >= 1 and S % patch == 0, f"patch_ranks: maps of {S} pixels are no whole patches of {patch!r}")
+            a.layout, a.g, a.patch = RANK_PIXEL, S // patch, patch
+        total = T * a.g * a.g
+        n = total if scope == "clip" else a.g * a.g
+    _require(n <= PERTURB_MAX_UNITS, f"patch_ranks: {n} units per ranking, at most {PERTURB_MAX_UNITS} are supported")
+    _require(B * total < 2 ** 31, f"patch_ranks: {B * total} units in all")
+    _on_device("patch_ranks", scores)
+    ranks = torch.empty(B, total, dtype=torch.int32, device=scores.device)
+    pooled = torch.empty(B, total, dtype=torch.float32, device=scores.device) if a.layout == RANK_PIXEL else None
+    a.scores, a.ranks, a.pooled, a.B, a.T = ptr(scores), ptr(ranks), ptr(pooled), B, T
+    a.scope = SCOPE_CLIP if scope == "clip" else SCOPE_FRAME
+    with torch.cuda.device(scores.device):
+        check(load().gava_patch_ranks(C.byref(a), stream_ptr(scores.device)), "gava_patch_ranks")
+    return ranks
+
+
+def blur_clips(x, taps, out=None):
+    """Separable Gaussian blur of every (b, c, t) plane of the fp32 clips x [B, 3, T, S, S] with the fp32 taps [2r + 1]
+    (gaussian_taps; r <= BLUR_MAX_RADIUS), the border replicated (gava_blur_clips).  -> out, shaped like x, allocated when not
+    given; a workspace of x's size is allocated for the row pass.  Two launches, no sync."""
+    _require(_is_f32(x) and x.dim() == 5 and x.shape[1] == 3 and x.shape[3] == x.shape[4] and x.numel() > 0,
+             "blur_clips: x must be a contiguous fp32 [B, 3, T, S, S] tensor")
+    _require(_is_f32(taps) and taps.dim() == 1 and taps.numel() % 2 == 1 and taps.numel() // 2 <= BLUR_MAX_RADIUS,
+             f"blur_clips: taps must be a contiguous fp32 [2r + 1] tensor with r <= {BLUR_MAX_RADIUS}")
+    _require(out is None or (_is_f32(out) and out.shape == x.shape and out.data_ptr() != x.data_ptr()),
+             "blur_clips: out must be a contiguous fp32 tensor shaped like x, and not x itself")
+    _require(x.is_cuda, "blur_clips: every tensor must be on the HIP device: there is no CPU fallback")
+    taps = taps.to(x.device)
+    _on_device("blur_clips", x, taps, out)
+    if out is None:
+        out = torch.empty_like(x)
+    tmp = torch.empty_like(x)
+    a = BlurClipsArgs()
+    a.x, a.taps, a.tmp, a.out = ptr(x), ptr(taps), ptr(tmp), ptr(out)
+    a.B, a.T, a.size, a.radius = x.shape[0], x.shape[2], x.shape[3], taps.numel() // 2
+    with torch.cuda.device(x.device):
+        check(load().gava_blur_clips(C.byref(a), stream_ptr(x.device)), "gava_blur_clips")
+    return out
+
+
+def perturb_clips(x, ranks, k, *, patch, mode, baseline=None, out=None):
+    """The perturbed copies of the fp32 clips x [nb, 3, T, S, S] (gava_perturb_clips).  ranks int32 [nb, T*(S/patch)^2] (patch
+    units, as patch_ranks writes them in either scope) or [nb, T] (frame units); k: a host list of S1 non-decreasing thresholds.
+    mode "deletion": a pixel takes the baseline when its unit's rank < k_s, else x; "insertion": the reverse.  baseline: None
+    (zero), fp32 [3] (one value per channel) or fp32 shaped like x.  -> out fp32 [nb, S1, 3, T, S, S], whose words are x's or
+    the baseline's bit for bit; allocated when not given.  One launch, no sync."""
+    _require(mode in ("deletion", "insertion"), f"perturb_clips: mode must be 'deletion' or 'insertion', got {mode!r}")
+    _require(_is_f32(x) and x.dim() == 5 and x.shape[1] == 3 and x.shape[3] == x.shape[4] and x.numel() > 0,
+             "perturb_clips: x must be a contiguous fp32 [nb, 3, T, S, S] tensor")
+    nb, _, T, S, _ = x.shape
+    _require(isinstance(patch, int) and patch >= 1 and S % patch == 0, f"perturb_clips: clips of {S} pixels are no whole patches of {patch!r}")
+    g = S // patch
+    _require(torch.is_tensor(ranks) and ranks.dtype == torch.int32 and ranks.is_contiguous() and ranks.dim() == 2 and ranks.shape[0] == nb
+             and ranks.shape[1] in (T, T * g * g),
+             f"perturb_clips: ranks must be a contiguous int32 [{nb}, {T * g * g}] (patch units) or [{nb}, {T}] (frame units) tensor")
+    units = UNITS_PATCH if ranks.shape[1] == T * g * g else UNITS_FRAME        # (g = 1: the two are the same thing)
+    try:
+        k = [int(v) for v in k]
+    except (TypeError, ValueError):
+        raise GavaError(f"perturb_clips: k must be a list of ints, got {k!r}") from None
+    _require(1 <= len(k) <= PERTURB_MAX_STEPS, f"perturb_clips: {len(k)} thresholds, between 1 and {PERTURB_MAX_STEPS} are supported")
+    _require(k[0] >= 0 and all(b >= a for a, b in zip(k, k[1:])) and k[-1] < 2 ** 31, f"perturb_clips: thresholds must be non-negative and non-decreasing, got {k}")
+    kind = BASELINE_ZERO
+    if baseline is not None:
+        _require(_is_f32(baseline) and (tuple(baseline.shape) == (3,) or baseline.shape == x.shape),
+                 f"perturb_clips: baseline must be None, a contiguous fp32 [3] tensor or one shaped like x, got "
+                 f"{(baseline.dtype, tuple(baseline.shape)) if torch.is_tensor(baseline) else type(baseline)}")
+        kind = BASELINE_CHANNEL if baseline.dim() == 1 else BASELINE_TENSOR
+    want = (nb, len(k), 3, T, S, S)
+    _require(out is None or (_is_f32(out) and tuple(out.shape) == want), f"perturb_clips: out must be a contiguous fp32 {want} tensor")
+    _on_device("perturb_clips", x, ranks, baseline, out)
+    if x.data_ptr() % 16:
+        x = x.clone()
+    if kind == BASELINE_TENSOR and baseline.data_ptr() % 16:
+        baseline = baseline.clone()
+    if out is None:
+        out = torch.empty(want, dtype=torch.float32, device=x.device)
+    _require(out.data_ptr() % 16 == 0, "perturb_clips: out must be 16-byte aligned")
+    a = PerturbClipsArgs()
+    a.x, a.ranks, a.baseline, a.out = ptr(x), ptr(ranks), ptr(baseline), ptr(out)
+    a.nb, a.T, a.size, a.patch, a.units = nb, T, S, patch, units
+    a.mode = PERTURB_DELETION if mode == "deletion" else PERTURB_INSERTION
+    a.baseline_kind, a.n_steps = kind, len(k)
+    for s, v in enumerate(k):
+        a.k[s] = v
+    with torch.cuda.device(x.device):
+        check(load().gava_perturb_clips(C.byref(a), stream_ptr(x.device)), "gava_perturb_clips")
+    return out
+
+
+def perturb_scores(logits, fractions, *, ref_step, target=None):
+    """The curves of a perturbation run (gava_perturb_scores).  logits fp32 [nb * S1, C] (clip-major, then step; rows
+    contiguous), fractions: a host list of S1 abscissae, target: int64 [nb] device tensor or None - then the top-1 class of
+    each clip's row ref_step, found on the device.
+    -> dict(logit fp32 [nb, S1] = the target's raw logit, prob fp32 [nb, S1] = its softmax probability, top1 int32 [nb, S1]
+    (lowest class on ties), auc_logit / auc_prob fp32 [nb] = trapezoids over the fractions, target int64 [nb]).  A target
+    outside [0, C) gives NaN for that clip's logit, prob and areas.  One launch, no sync."""
+    try:
+        f = [float(v) for v in fractions]
+    except (TypeError, ValueError):
+        raise GavaError(f"perturb_scores: fractions must be a list of numbers, got {fractions!r}") from None
+    S1 = len(f)
+    _require(1 <= S1 <= PERTURB_MAX_STEPS, f"perturb_scores: {S1} fractions, between 1 and {PERTURB_MAX_STEPS} are supported")
+    _require(torch.is_tensor(logits) and logits.dtype == torch.float32 and logits.dim() == 2 and logits.shape[1] >= 1
+             and (logits.shape[1] == 1 or logits.stride(1) == 1) and logits.stride(0) >= logits.shape[1],
+             "perturb_scores: logits must be an fp32 [nb * S1, C] tensor with contiguous rows")
+    _require(logits.shape[0] > 0 and logits.shape[0] % S1 == 0, f"perturb_scores: {logits.shape[0]} rows are no whole clips of {S1} steps")
+    nb, Cn = logits.shape[0] // S1, logits.shape[1]
+    _require(isinstance(ref_step, int) and 0 <= ref_step < S1, f"perturb_scores: ref_step {ref_step!r} is outside the {S1} steps")
+    _require(target is None or (torch.is_tensor(target) and target.dtype == torch.int64 and tuple(target.shape) == (nb,) and target.is_contiguous()),
+             f"perturb_scores: target must be None or a contiguous int64 [{nb}] tensor")
+    _on_device("perturb_scores", logits, target)
+    dev = logits.device
+    res = dict(logit=torch.empty(nb, S1, dtype=torch.float32, device=dev), prob=torch.empty(nb, S1, dtype=torch.float32, device=dev),
+               top1=torch.empty(nb, S1, dtype=torch.int32, device=dev), auc_logit=torch.empty(nb, dtype=torch.float32, device=dev),
+               auc_prob=torch.empty(nb, dtype=torch.float32, device=dev), target=torch.empty(nb, dtype=torch.int64, device=dev))
+    a = PerturbScoresArgs()
+    a.logits, a.ld, a.target = ptr(logits), logits.stride(0), ptr(target)
+    a.logit, a.prob, a.top1 = ptr(res["logit"]), ptr(res["prob"]), ptr(res["top1"])
+    a.auc_logit, a.auc_prob, a.target_out = ptr(res["auc_logit"]), ptr(res["auc_prob"]), ptr(res["target"])
+    a.nb, a.n_steps, a.C, a.ref_step = nb, S1, Cn, ref_step
+    for s, v in enumerate(f):
+        a.fractions[s] = v
+    with torch.cuda.device(dev):
+        check(load().gava_perturb_scores(C.byref(a), stream_ptr(dev)), "gava_perturb_scores")
+    return res
 
 
 # ---- backward ops (SURVEY 8f row 1) ------------------------------------------------------------

@@ -861,6 +861,42 @@ class RelevanceMaps:
         return "RelevanceMaps(" + ", ".join(f"{k}={tuple(getattr(self, k).shape)}" for k in self.__slots__) + ")"
 
 
+class PerturbationCurves:
+    """What VitaCLIP.perturbation_curves returns, B clips and S1 steps:
+      mode                 "deletion" or "insertion"
+      fractions [S1]       fp32 HOST tensor: the share of a ranking's units perturbed at each step (the curves' abscissae)
+      logit     [B, S1]    fp32: the target's raw logit on the perturbed clip
+      prob      [B, S1]    fp32: its softmax probability
+      top1      [B, S1]    int32: the perturbed clip's top-1 class (lowest class on ties)
+      auc_logit, auc_prob [B]  fp32: the areas under the two curves (trapezoids over fractions)
+      target    [B]        int64: the class each clip was asked about
+      ranks     [B, n]     int32: the ranking the perturbation followed, per unit in the scores' own order (0 = first)
+    everything but fractions on the device."""
+    __slots__ = ("mode", "fractions", "logit", "prob", "top1", "auc_logit", "auc_prob", "target", "ranks")
+
+    def __init__(self, mode, fractions, logit, prob, top1, auc_logit, auc_prob, target, ranks):
+        self.mode, self.fractions, self.logit, self.prob, self.top1 = mode, fractions, logit, prob, top1
+        self.auc_logit, self.auc_prob, self.target, self.ranks = auc_logit, auc_prob, target, ranks
+
+    def __repr__(self):
+        return f"PerturbationCurves(mode={self.mode!r}, " + ", ".join(f"{k}={tuple(getattr(self, k).shape)}" for k in self.__slots__[1:]) + ")"
+
+
+class Faithfulness(dict):
+    """What VitaCLIP.faithfulness returns: {method: {"deletion": PerturbationCurves, "insertion": PerturbationCurves}}, the
+    methods in the order asked for and the control "random" last.  table() is the text a user reads: per method the mean
+    areas over the clips (a faithful map has a LOW deletion area and a HIGH insertion area; "random" is the floor to beat).
+    table() copies the areas to the host, so it waits for the device; building the object does not."""
+
+    def table(self):
+        rows = [f"{'method':<12}{'del auc_prob':>14}{'ins auc_prob':>14}{'del auc_logit':>15}{'ins auc_logit':>15}"]
+        for name, c in self.items():
+            d, i = c["deletion"], c["insertion"]
+            rows.append(f"{name:<12}{float(d.auc_prob.mean()):>14.4f}{float(i.auc_prob.mean()):>14.4f}"
+                        f"{float(d.auc_logit.mean()):>15.4f}{float(i.auc_logit.mean()):>15.4f}")
+        return "\n".join(rows)
+
+
 class VitaCLIP(nn.Module, _HipHost):
 
     def __init__(
@@ -1426,6 +1462,161 @@ class VitaCLIP(nn.Module, _HipHost):
             self.text_features = self.text_features.detach()        # the last reference into this call's graph
         state.pop("r", None)
         return request.pop("out"), logits.detach(), target
+
+    def perturbation_curves(self, x, scores, mode="deletion", target=None, steps=10, fractions=None, scope="clip",
+                            baseline="zero", blur_sigma=5.0, max_clips=None):
+        """How faithful an importance map is to the model: the deletion or insertion curve of every clip (Petsiuk et al.,
+        "RISE"; the test Chefer et al. report for relevance) -> PerturbationCurves (see there for the fields).
+          mode="deletion"   the most important units are replaced by the baseline first: the target's score should FALL fast
+          mode="insertion"  start from the baseline and put the most important units back first: it should RISE fast
+        x: fp32 device clips [B, 3, T, S, S], as for saliency.  scores: what to rank by, fp32 on x's device -
+        [B, T, g, g] (patches, g = S / P: attention_maps(x).patches, relevance_maps(x).patches), [B, T, S, S] (pixels, summed
+        over each patch: saliency(x)[0]) or [B, T] (frames: the maps' .cls, or any per-frame score).  scope="clip" ranks all
+        units of a clip together, scope="frame" the patches of every frame among themselves (every frame then loses the same
+        number of patches per step; refused for frame scores).  The order is exact: descending, ties to the lower index,
+        NaNs last (gava_patch_ranks).
+        fractions: the share of a ranking's n units perturbed at each step - by default linspace(0, 1, steps + 1), else a
+        strictly increasing list from 0 to 1; step s perturbs the k_s = floor(f_s n + 0.5) first units of the ranking.
+        baseline: "zero" (the dataset's mean colour, in the normalised space clips live in), "blur" (the clip itself under a
+        Gaussian of blur_sigma pixels, radius ceil(3 sigma), border replicated), an fp32 tensor [3] (one value per channel) or
+        one shaped like x.  target: as for saliency - None (each clip's top-1 class on its UNPERTURBED step, picked on the
+        device), an int (checked on the host) or an int64 [B] device tensor (out of range: that clip's curves are NaN).
+        Evaluation only: call it under torch.no_grad() on a model in eval() mode.  The S1 = len(fractions) perturbed copies
+        of a clip are written by one kernel (gava_perturb_clips) and go through the plain forward, max(1, max_clips // S1)
+        whole clips at a time; max_clips defaults to the most clips one launch's grid covers (65535 frames).  A chunk's
+        nb * S1 perturbed clips are in memory at once (4.8 MB each at 224 px and T = 8) next to the forward's workspace: lower
+        max_clips for big batches.  Chunking changes no bit.  The text features are cached for the duration of the call (cache_text_features is restored afterwards).  The
+        call ends with one gava_perturb_scores launch over all clips and never waits for the device.
+        Several ranks: every rank passes its own clips and gets the curves of its own clips (the forward gathers the
+        perturbed clips' features of all ranks, local_logits() takes this rank's rows back out); every rank must therefore
+        pass the same B, the same number of fractions and the same max_clips."""
+        what = "perturbation_curves"
+        if torch.is_grad_enabled() or self.training:
+            raise hip.GavaError(f"{what} is an evaluation path: call it under torch.no_grad() on a model in eval() mode")
+        if mode not in ("deletion", "insertion"):
+            raise hip.GavaError(f"{what}: mode must be 'deletion' or 'insertion', got {mode!r}")
+        if scope not in ("clip", "frame"):
+            raise hip.GavaError(f"{what}: scope must be 'clip' or 'frame', got {scope!r}")
+        sh = self._shape
+        S, P = sh["size"], sh["P"]
+        if not (torch.is_tensor(x) and x.dim() == 5 and x.is_floating_point() and x.shape[1] == 3 and x.shape[3] == x.shape[4] == S
+                and x.shape[0] > 0 and x.shape[2] > 0):
+            raise hip.GavaError(f"{what} takes a floating-point clip batch [B, 3, T, {S}, {S}], got "
+                                f"{(x.dtype, tuple(x.shape)) if torch.is_tensor(x) else type(x)}")
+        B, T, g = x.shape[0], x.shape[2], S // P
+        layouts = {(B, T, g, g): "patch", (B, T, S, S): "pixel", (B, T): "frame"}
+        if not (torch.is_tensor(scores) and scores.is_floating_point() and tuple(scores.shape) in layouts):
+            raise hip.GavaError(f"{what}: scores must be a floating-point [{B}, {T}, {g}, {g}] (patches), [{B}, {T}, {S}, {S}] (pixels) or "
+                                f"[{B}, {T}] (frames) tensor, got {(scores.dtype, tuple(scores.shape)) if torch.is_tensor(scores) else type(scores)}")
+        layout = layouts[tuple(scores.shape)]
+        if layout == "frame" and scope == "frame":
+            raise hip.GavaError(f"{what}: scope='frame' ranks the patches of a frame; frame scores have one unit per frame")
+        n = T if layout == "frame" else T * g * g if scope == "clip" else g * g
+        if n > hip.PERTURB_MAX_UNITS:
+            raise hip.GavaError(f"{what}: {n} units per ranking, at most {hip.PERTURB_MAX_UNITS} are supported")
+        fr, ks = hip.perturb_thresholds(n, steps, fractions)
+        S1 = len(fr)
+        if self.use_text_prompt_learning and self.prompt_learner.n_kv is None:
+            raise hip.GavaError(f"{what}: a per-descriptor (use_descriptor / desc_wise) head has no single logit per class")
+        n_cls = self.prompt_learner.n_cls if self.use_text_prompt_learning else self.text_features.shape[0]
+        if target is not None and not torch.is_tensor(target):
+            if not 0 <= int(target) < n_cls:
+                raise hip.GavaError(f"{what}: target {target} is outside the {n_cls} classes")
+        elif target is not None and not (target.dtype == torch.int64 and tuple(target.shape) == (B,)):
+            raise hip.GavaError(f"{what}: a tensor target must be int64 [{B}] on the device")
+        kind = baseline if isinstance(baseline, str) else "tensor"
+        if kind not in ("zero", "blur", "tensor") or (kind == "tensor" and not (
+                torch.is_tensor(baseline) and baseline.is_floating_point() and (tuple(baseline.shape) == (3,) or baseline.shape == x.shape))):
+            raise hip.GavaError(f"{what}: baseline must be 'zero', 'blur', a floating-point tensor [3] or one shaped like x, got "
+                                f"{(baseline.dtype, tuple(baseline.shape)) if torch.is_tensor(baseline) else baseline!r}")
+        taps = hip.gaussian_taps(blur_sigma) if kind == "blur" else None
+        fit = hip.MAX_GRID_FRAMES // T
+        if fit < S1:
+            raise hip.GavaError(f"{what}: one clip's {S1} steps x {T} frames are past the {hip.MAX_GRID_FRAMES} frames one launch covers")
+        step = max(1, (fit if max_clips is None else min(fit, int(max_clips))) // S1)
+        if not x.is_cuda or not scores.is_cuda or (torch.is_tensor(target) and not target.is_cuda):
+            raise hip.GavaError("VitaCLIP (gava_clip_amd) runs on the HIP device only: move the model and the "
+                                "input with .cuda(); there is no CPU fallback")
+        dev = x.device
+        cached = self.cache_text_features
+        self.cache_text_features = True
+        try:
+            with torch.cuda.device(dev):
+                x = x.detach().float().contiguous()
+                ranks = hip.patch_ranks(scores.detach().to(dev).float().contiguous(), patch=P if layout == "pixel" else None, scope=scope)
+                if kind == "zero":
+                    base = None
+                elif kind == "blur":
+                    base = hip.blur_clips(x, taps)
+                else:
+                    base = baseline.detach().to(dev).float().contiguous()
+                if target is not None and not torch.is_tensor(target):
+                    target = torch.full((B,), int(target), dtype=torch.int64, device=dev)
+                logits = None
+                for i in range(0, B, step):
+                    nb = min(step, B - i)
+                    b = base[i:i + nb] if base is not None and base.dim() == 5 else base
+                    xp = hip.perturb_clips(x[i:i + nb], ranks[i:i + nb], ks, patch=P, mode=mode, baseline=b)
+                    lg = self.local_logits(self._forward_impl(xp.view(nb * S1, 3, T, S, S), None, None, False)[0])
+                    if nb == B:
+                        logits = lg
+                        break
+                    if logits is None:
+                        logits = torch.empty(B * S1, lg.shape[-1], dtype=torch.float32, device=dev)
+                    logits[i * S1:(i + nb) * S1] = lg
+                self.last["local_batch"] = B
+                res = hip.perturb_scores(logits, fr, ref_step=0 if mode == "deletion" else S1 - 1,
+                                         target=target.contiguous() if target is not None else None)
+        finally:
+            self.cache_text_features = cached
+        return PerturbationCurves(mode, torch.tensor(fr, dtype=torch.float32), res["logit"], res["prob"], res["top1"],
+                                  res["auc_logit"], res["auc_prob"], res["target"], ranks)
+
+    _FAITHFULNESS_METHODS = ("rollout", "relevance", "saliency")
+
+    def faithfulness(self, x, methods=("rollout", "relevance", "saliency"), target=None, seed=0, **kw):
+        """Which map to believe for this model and these clips: both perturbation curves of every method's map, for one and
+        the same target, next to a random ranking -> Faithfulness, {name: {"deletion": ..., "insertion": ...}}; print its
+        .table().  methods: any of "rollout" (attention_maps(x).patches), "relevance" (relevance_maps(x, target).patches) and
+        "saliency" (saliency(x, target)[0], pixels pooled to patches); the control "random" ranks by uniform scores drawn from
+        a device generator seeded with `seed`, so a call repeats bit for bit.  target: as for perturbation_curves; None is the
+        top-1 class of the plain forward of x, picked on the device once and used for every method.  **kw goes to
+        perturbation_curves (steps, fractions, scope, baseline, blur_sigma, max_clips; not mode).  Evaluation only, like
+        perturbation_curves; the maps' own rules apply to x (whole num_frames groups).  Nothing waits for the device."""
+        if torch.is_grad_enabled() or self.training:
+            raise hip.GavaError("faithfulness is an evaluation path: call it under torch.no_grad() on a model in eval() mode")
+        methods = tuple(methods)
+        if not methods or any(m not in self._FAITHFULNESS_METHODS for m in methods) or len(set(methods)) != len(methods):
+            raise hip.GavaError(f"faithfulness: methods must be distinct names out of {self._FAITHFULNESS_METHODS}, got {methods!r}")
+        if "mode" in kw:
+            raise hip.GavaError("faithfulness runs both modes: mode is not an argument")
+        if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 5):
+            raise hip.GavaError("faithfulness takes a device clip batch [B, 3, T, S, S]: there is no CPU fallback")
+        B, T = x.shape[0], x.shape[2]
+        g = self._shape["size"] // self._shape["P"]
+        with torch.cuda.device(x.device):
+            if target is None:
+                target = self.local_logits(self._forward_impl(x, None, None, False)[0]).argmax(dim=1)
+            elif not torch.is_tensor(target):
+                n_cls = self.prompt_learner.n_cls if self.use_text_prompt_learning else self.text_features.shape[0]
+                if not 0 <= int(target) < n_cls:
+                    raise hip.GavaError(f"faithfulness: target {target} is outside the {n_cls} classes")
+                target = torch.full((B,), int(target), dtype=torch.int64, device=x.device)
+            maps = {}
+            for m in methods:
+                if m == "rollout":
+                    maps[m] = self.attention_maps(x).patches
+                elif m == "relevance":
+                    maps[m] = self.relevance_maps(x, target).patches
+                else:
+                    maps[m] = self.saliency(x, target)[0]
+            gen = torch.Generator(device=x.device)
+            gen.manual_seed(int(seed))
+            maps["random"] = torch.rand(B, T, g, g, generator=gen, dtype=torch.float32, device=x.device)
+            out = Faithfulness()
+            for name, s in maps.items():
+                out[name] = {md: self.perturbation_curves(x, s.detach().contiguous(), mode=md, target=target, **kw) for md in ("deletion", "insertion")}
+        return out
 
     def _maps_logits(self, video):
         """The inference head (gava_similarity_head) on this rank's clip features; text features from the cache when it is

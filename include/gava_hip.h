@@ -892,6 +892,106 @@ int gava_attention_relevance(const gava_attention_relevance_args* a, gava_stream
 /* sizeof of gava_attention_relevance_args, like gava_attention_maps_struct_sizes.  Writes min(cap, 1) entries, returns 1. */
 int gava_attention_relevance_struct_sizes(size_t* out, int cap);
 
+/* ---- faithfulness curves: deletion / insertion by patch or frame -------------------------------------------------------------
+ *
+ * The perturbation test of an importance map (Petsiuk et al., RISE; Chefer et al. for relevance): rank a clip's patches or
+ * frames by a score map (gava_patch_ranks), build for each of S1 thresholds the clip with its k_s most important units
+ * replaced by a baseline - or with only those kept - (gava_perturb_clips; the baseline may be the blurred clip,
+ * gava_blur_clips), run the plain forward on the nb * S1 clips, and reduce the logits to the curves and the areas under them
+ * (gava_perturb_scores).  None of the four uses an atomic: a call repeats bit for bit.  One launch each on `stream`, except
+ * gava_blur_clips (two: rows, then columns) and gava_patch_ranks on pixel scores (two: pool, then rank).
+ *
+ * gava_patch_ranks.  scores fp32, by layout:
+ *   GAVA_RANK_PATCH  [B][T][g][g]                the unit is a patch
+ *   GAVA_RANK_PIXEL  [B][T][g*patch][g*patch]    a patch's score is the fp32 sum of its patch x patch pixels, formed by a launch of
+ *                                                its own into `pooled`: a wave per patch, lane l adds pixels l, l + 64, ... of the
+ *                                                patch (row-major) in that order, then a fixed xor butterfly over the lanes
+ *   GAVA_RANK_FRAME  [B][T]                      the unit is a frame (g, patch ignored)
+ * scope GAVA_SCOPE_CLIP: one ranking per clip over its n = T*g*g patches (n = T frames); GAVA_SCOPE_FRAME: one ranking per
+ * frame over its n = g*g patches (patch units only).  ranks int32, [B][T*g*g] (or [B][T]) in the scores' own unit order.
+ * Unit j comes BEFORE unit i when s_j > s_i, or s_j == s_i (so -0 == +0) and j < i; every NaN comes after -inf, NaNs among
+ * themselves by index.  rank_i = #{j : j before i}: 0 is the most important unit, the ranks of a ranking are a permutation
+ * of 0 .. n-1.  Counted, not sorted: a workgroup owns 256 units of one ranking and streams all n scores of it through LDS.
+ * GAVA_EINVAL: null args / scores / ranks, B, T, g < 1, patch < 1 or no `pooled` in the pixel layout, an unknown layout or scope, the frame
+ * scope with the frame layout, n > GAVA_PERTURB_MAX_UNITS, more than 2^31 - 1 units or rankings in all.
+ *
+ * gava_blur_clips.  Separable Gaussian blur of every one of the B*3*T planes of x fp32 [B][3][T][size][size] -> out, the same
+ * shape; taps: DEVICE fp32 [2*radius + 1], applied along x then along y with the border replicated (indices clamped), each
+ * output a chain of fused multiply-adds over the taps in ascending order.  tmp: fp32 workspace of x's size (the row pass's
+ * output); x, tmp and out are three different buffers.  GAVA_EINVAL: a null pointer, B, T or size < 1, radius outside
+ * [0, GAVA_BLUR_MAX_RADIUS].
+ *
+ * gava_perturb_clips.  x fp32 [nb][3][T][size][size]; ranks as gava_patch_ranks writes them, [nb][T*g*g] (units
+ * GAVA_UNITS_PATCH, g = size/patch) or [nb][T] (GAVA_UNITS_FRAME); k[0 .. n_steps): the thresholds, by value, non-decreasing.
+ * out fp32 [nb][n_steps][3][T][size][size]:
+ *   GAVA_PERTURB_DELETION   out[b][s] = rank(unit of the pixel) < k[s] ? baseline : x
+ *   GAVA_PERTURB_INSERTION  out[b][s] = rank(unit of the pixel) < k[s] ? x : baseline
+ * a selection: every output word is x's or the baseline's, bit for bit.  baseline: GAVA_BASELINE_ZERO (+0.0f), _CHANNEL
+ * (baseline = DEVICE fp32 [3], one value per channel) or _TENSOR (baseline fp32 shaped like x).  x is read once and written
+ * n_steps times, 16 bytes per lane when patch is a multiple of 4, 8 when it is even (P = 14), single floats otherwise.
+ * Offsets are 64-bit: out may hold more than 2^31 elements.  GAVA_EINVAL: null args / x / ranks / out, a baseline pointer that
+ * does not go with the kind, nb, T, size, patch < 1 or size % patch != 0, n_steps outside [1, GAVA_PERTURB_MAX_STEPS], a
+ * negative or decreasing k, an unknown mode / units / kind, x / out / a tensor baseline not 16-byte aligned.
+ *
+ * gava_perturb_scores.  logits fp32, nb * n_steps rows of C (row b * n_steps + s, rows ld floats apart); target: DEVICE int64
+ * [nb] or NULL - then clip b's target is the top-1 class of its row ref_step (the unperturbed step), found here; fractions:
+ * the curves' abscissae, by value.  Per clip and step: logit = the target's raw logit (a copy), prob = its softmax
+ * probability (fp32: exp(x_t - max) / sum_c exp(x_c - max), lanes stride the classes, a xor butterfly), top1 = the row's
+ * largest logit, the lowest class on ties (0 for a row of NaNs).  Per clip: auc = sum_s (f_s - f_{s-1}) * (y_s + y_{s-1}) / 2
+ * for y = logit and y = prob, added in step order in fp32 (0 for n_steps = 1), and target_out = the target used.  A target
+ * outside [0, C) is not read through: that clip's logit, prob and both areas are NaN, top1 and target_out are written as
+ * usual.  One workgroup per clip.  GAVA_EINVAL: null args or a null logits / logit / prob / top1 / auc / target_out pointer,
+ * nb or C < 1, ld < C, n_steps outside [1, GAVA_PERTURB_MAX_STEPS], ref_step outside [0, n_steps). */
+#define GAVA_PERTURB_MAX_UNITS 65536
+#define GAVA_PERTURB_MAX_STEPS 128
+#define GAVA_BLUR_MAX_RADIUS 64
+#define GAVA_RANK_PATCH 0
+#define GAVA_RANK_PIXEL 1
+#define GAVA_RANK_FRAME 2
+#define GAVA_SCOPE_CLIP 0
+#define GAVA_SCOPE_FRAME 1
+#define GAVA_UNITS_PATCH 0
+#define GAVA_UNITS_FRAME 1
+#define GAVA_PERTURB_DELETION 0
+#define GAVA_PERTURB_INSERTION 1
+#define GAVA_BASELINE_ZERO 0
+#define GAVA_BASELINE_CHANNEL 1
+#define GAVA_BASELINE_TENSOR 2
+typedef struct {
+  const float* scores; int32_t* ranks;
+  float* pooled;                               /* GAVA_RANK_PIXEL: fp32 workspace [B][T][g][g]; ignored otherwise */
+  int B, T, g, patch, layout, scope;
+} gava_patch_ranks_args;
+int gava_patch_ranks(const gava_patch_ranks_args* a, gava_stream_t stream);
+
+typedef struct {
+  const float* x; const float* taps; float* tmp; float* out;
+  int B, T, size, radius;
+} gava_blur_clips_args;
+int gava_blur_clips(const gava_blur_clips_args* a, gava_stream_t stream);
+
+typedef struct {
+  const float* x; const int32_t* ranks; const float* baseline; float* out;
+  int nb, T, size, patch, units, mode, baseline_kind, n_steps;
+  int k[GAVA_PERTURB_MAX_STEPS];
+} gava_perturb_clips_args;
+int gava_perturb_clips(const gava_perturb_clips_args* a, gava_stream_t stream);
+
+typedef struct {
+  const float* logits; int64_t ld;
+  const int64_t* target;                       /* DEVICE [nb] or NULL */
+  float* logit; float* prob; int32_t* top1;    /* [nb][n_steps] */
+  float* auc_logit; float* auc_prob;           /* [nb] */
+  int64_t* target_out;                         /* [nb] */
+  int nb, n_steps, C, ref_step;
+  float fractions[GAVA_PERTURB_MAX_STEPS];
+} gava_perturb_scores_args;
+int gava_perturb_scores(const gava_perturb_scores_args* a, gava_stream_t stream);
+
+/* sizeof of gava_patch_ranks_args, gava_blur_clips_args, gava_perturb_clips_args, gava_perturb_scores_args, in that order,
+ * like gava_attention_relevance_struct_sizes.  Writes min(cap, 4) entries, returns 4. */
+int gava_perturbation_struct_sizes(size_t* out, int cap);
+
 /* sizeof of every ABI struct as the library was compiled, in the order gemm_args, layernorm_args, attention_args,
  * attention_f32_args, clip_desc, vision_layer, vision_layer8, vision_model, text_layer, text_model, layernorm_bwd_args,
  * attention_bwd_args, vision_saved, preprocess_args, patchify_args, preprocess_clips_args, view_scores_args.  Writes
