@@ -37,7 +37,8 @@ EXPORTS = ["gava_abi_version", "gava_gemm", "gava_layernorm", "gava_attention",
            "gava_unpatchify", "gava_input_grad_struct_sizes",
            "gava_attention_mass", "gava_attention_maps_struct_sizes",
            "gava_attention_relevance", "gava_attention_relevance_struct_sizes",
-           "gava_patch_ranks", "gava_blur_clips", "gava_perturb_clips", "gava_perturb_scores", "gava_perturbation_struct_sizes"]
+           "gava_patch_ranks", "gava_blur_clips", "gava_perturb_clips", "gava_perturb_scores", "gava_perturbation_struct_sizes",
+           "gava_path_clips", "gava_clip_range", "gava_unpatchify_path", "gava_path_delta", "gava_path_grad_struct_sizes"]
 ATTENTION_MASS_MAX_KEYS = 640     # gava_attention_mass keeps K of one (frame, head) resident in LDS
 ATTENTION_RELEVANCE_MAX_KEYS = 640     # and so does gava_attention_relevance
 PERTURB_MAX_UNITS = 65536         # patches or frames one gava_patch_ranks ranking holds
@@ -48,6 +49,10 @@ SCOPE_CLIP, SCOPE_FRAME = 0, 1
 UNITS_PATCH, UNITS_FRAME = 0, 1
 PERTURB_DELETION, PERTURB_INSERTION = 0, 1
 BASELINE_ZERO, BASELINE_CHANNEL, BASELINE_TENSOR = 0, 1, 2
+PATH_MAX_STEPS = 64               # copies of a clip gava_path_clips writes and gava_unpatchify_path reduces (alpha / w by value)
+CLIP_RANGE_PARTS = 64             # workgroups per clip in gava_clip_range's first launch
+PATH_LINE, PATH_NOISE = 0, 1      # gava_path_clips_args.mode
+PATH_GRAD, PATH_ABSMAX, PATH_L2, PATH_ATTR, PATH_ATTR_SUM, PATH_ATTR_ABS = 0, 1, 2, 3, 4, 5      # gava_unpatchify_path_args.mode
 ADAMW_MAX_GROUPS = 8
 
 _vp, _fp, _ip = C.c_void_p, C.c_void_p, C.c_void_p  # all device pointers travel as void*
@@ -279,6 +284,32 @@ class PerturbScoresArgs(C.Structure):
                 ("fractions", C.c_float * PERTURB_MAX_STEPS)]
 
 
+class PathClipsArgs(C.Structure):
+    _fields_ = [("x", _fp), ("baseline", _fp), ("sigma", _fp), ("out", _fp),
+                ("nb", C.c_int), ("T", C.c_int), ("size", C.c_int), ("patch", C.c_int), ("mode", C.c_int),
+                ("baseline_kind", C.c_int), ("m", C.c_int), ("clip0", C.c_int), ("seed", C.c_uint64),
+                ("alpha", C.c_float * PATH_MAX_STEPS), ("beta", C.c_float * PATH_MAX_STEPS)]
+
+
+class ClipRangeArgs(C.Structure):
+    _fields_ = [("x", _fp), ("min", _fp), ("max", _fp), ("sigma", _fp), ("workspace", _fp),
+                ("nb", C.c_int), ("T", C.c_int), ("size", C.c_int), ("rel", C.c_float)]
+
+
+class UnpatchifyPathArgs(C.Structure):
+    _fields_ = [("dpatch", _fp), ("ld", C.c_int64), ("x", _fp), ("baseline", _fp), ("out", _fp),
+                ("B", C.c_int), ("T", C.c_int), ("size", C.c_int), ("patch", C.c_int), ("mode", C.c_int),
+                ("baseline_kind", C.c_int), ("frame_rows", C.c_int), ("row_offset", C.c_int), ("m", C.c_int), ("reserved", C.c_int),
+                ("w", C.c_float * PATH_MAX_STEPS)]
+
+
+class PathDeltaArgs(C.Structure):
+    _fields_ = [("map", _fp), ("logits", _fp), ("ld", C.c_int64), ("target", _ip),
+                ("sum_attr", _fp), ("f_diff", _fp), ("delta", _fp),
+                ("B", C.c_int), ("T", C.c_int), ("size", C.c_int), ("m", C.c_int), ("C", C.c_int),
+                ("k_lo", C.c_int), ("k_hi", C.c_int), ("reserved", C.c_int)]
+
+
 class VisionSaved(C.Structure):
     _fields_ = [("e0", _fp), ("x", _fp), ("x1", _fp), ("qkv", _vp), ("pre", _vp), ("sidekv", _vp),
                 ("last_q", _vp), ("last_x1", _fp), ("last_pre", _vp)]
@@ -482,6 +513,18 @@ def load():
     if lib.gava_perturbation_struct_sizes(sizes, len(perturbation_mirrors)) != len(perturbation_mirrors):
         raise GavaError("libgava_hip.so and gava_clip_amd/hip.py disagree on the number of perturbation ABI structs")
     for cls, sz in zip(perturbation_mirrors, sizes):
+        if C.sizeof(cls) != sz:
+            raise GavaError(f"ctypes mirror {cls.__name__} is {C.sizeof(cls)} bytes, the library's struct {sz}: gava_clip_amd/hip.py is out of "
+                            f"step with include/gava_hip.h")
+    # the path gradients' structs, the same way
+    path_mirrors = [PathClipsArgs, ClipRangeArgs, UnpatchifyPathArgs, PathDeltaArgs]
+    for name, cls in (("gava_path_clips", PathClipsArgs), ("gava_clip_range", ClipRangeArgs),
+                      ("gava_unpatchify_path", UnpatchifyPathArgs), ("gava_path_delta", PathDeltaArgs)):
+        getattr(lib, name).argtypes, getattr(lib, name).restype = [C.POINTER(cls), _vp], C.c_int
+    lib.gava_path_grad_struct_sizes.argtypes, lib.gava_path_grad_struct_sizes.restype = [C.POINTER(C.c_size_t), C.c_int], C.c_int
+    if lib.gava_path_grad_struct_sizes(sizes, len(path_mirrors)) != len(path_mirrors):
+        raise GavaError("libgava_hip.so and gava_clip_amd/hip.py disagree on the number of path-gradient ABI structs")
+    for cls, sz in zip(path_mirrors, sizes):
         if C.sizeof(cls) != sz:
             raise GavaError(f"ctypes mirror {cls.__name__} is {C.sizeof(cls)} bytes, the library's struct {sz}: gava_clip_amd/hip.py is out of "
                             f"step with include/gava_hip.h")
@@ -965,6 +1008,192 @@ def perturb_scores(logits, fractions, *, ref_step, target=None):
         a.fractions[s] = v
     with torch.cuda.device(dev):
         check(load().gava_perturb_scores(C.byref(a), stream_ptr(dev)), "gava_perturb_scores")
+    return res
+
+
+# ---- path gradients: integrated gradients and SmoothGrad (gava_hip.h, "path gradients") -------------------------------------------
+
+def path_rule(rule, steps):
+    """The quadrature of integrated gradients on [0, 1] -> (alpha, w), two host lists of m floats (float64 arithmetic).
+    "trapezoid": m = steps >= 2 points alpha_k = k / (m - 1), weights 1 / (m - 1) with the two end ones halved; the baseline and
+    the clip itself are steps 0 and m - 1.  "gausslegendre": the steps >= 1 Gauss-Legendre nodes (numpy.polynomial.legendre.
+    leggauss) mapped to [0, 1], between the two endpoints as zero-weight steps: m = steps + 2 (the endpoints cost two forwards
+    and backwards of a clip and add nothing to the map; they are there for f(x0) and f(x)).  The weights sum to 1."""
+    _require(rule in ("trapezoid", "gausslegendre"), f"path_rule: rule must be 'trapezoid' or 'gausslegendre', got {rule!r}")
+    _require(isinstance(steps, int) and not isinstance(steps, bool), f"path_rule: steps must be an int, got {steps!r}")
+    if rule == "trapezoid":
+        _require(steps >= 2, f"path_rule: the trapezoid rule needs steps >= 2, got {steps}")
+        m = steps
+        alpha = [k / (m - 1) for k in range(m)]
+        w = [(0.5 if k in (0, m - 1) else 1.0) / (m - 1) for k in range(m)]
+    else:
+        _require(steps >= 1, f"path_rule: the Gauss-Legendre rule needs steps >= 1, got {steps}")
+        import numpy as np
+        t, wt = np.polynomial.legendre.leggauss(steps)
+        alpha = [0.0] + [float(0.5 * (v + 1.0)) for v in t] + [1.0]
+        w = [0.0] + [float(0.5 * v) for v in wt] + [0.0]
+        m = steps + 2
+    _require(m <= PATH_MAX_STEPS, f"path_rule: {m} steps (endpoints included), at most {PATH_MAX_STEPS} are supported")
+    return alpha, w
+
+
+def _float_list(what, v, lo, hi):
+    import math
+    try:
+        v = [float(s) for s in (v.tolist() if torch.is_tensor(v) else v)]
+    except (TypeError, ValueError):
+        raise GavaError(f"{what} must be a list of numbers, got {v!r}") from None
+    _require(lo <= len(v) <= hi, f"{what}: {len(v)} values, between {lo} and {hi} are supported")
+    _require(all(math.isfinite(s) for s in v), f"{what} must be finite, got {v}")
+    return v
+
+
+def _clip_baseline(what, x, baseline):
+    """-> the baseline kind of None / fp32 [3] / fp32 shaped like x."""
+    if baseline is None:
+        return BASELINE_ZERO
+    _require(_is_f32(baseline) and (tuple(baseline.shape) == (3,) or baseline.shape == x.shape),
+             f"{what}: baseline must be None, a contiguous fp32 [3] tensor or one shaped like x, got "
+             f"{(baseline.dtype, tuple(baseline.shape)) if torch.is_tensor(baseline) else type(baseline)}")
+    return BASELINE_CHANNEL if baseline.dim() == 1 else BASELINE_TENSOR
+
+
+def path_clips(x, *, patch, alpha=None, baseline=None, sigma=None, samples=None, seed=0, clip0=0, out=None):
+    """The m near-copies of the fp32 clips x [nb, 3, T, S, S] (gava_path_clips) -> out fp32 [nb, m, 3, T, S, S], allocated when
+    not given.  Either the straight line from a baseline - alpha: a host list of m values in [0, 1], out[b, k] = fma(alpha_k, x,
+    (1 - alpha_k) x0), exactly x0 at 0 and x at 1; baseline: None (zero), fp32 [3] or fp32 shaped like x - or Gaussian noise -
+    sigma: fp32 [nb] device tensor, samples = m, out[b, k] = fma(sigma_b, z, x) with z from Philox4x32-10 keyed by `seed` and
+    counted by (element, k, clip0 + b): clip0 is the global index of x[0], so a batch cut into calls gets the same noise.
+    One launch, no sync."""
+    what = "path_clips"
+    _require((alpha is None) != (sigma is None), f"{what}: give alpha (the line from a baseline) or sigma (noise), not both and not neither")
+    _require(_is_f32(x) and x.dim() == 5 and x.shape[1] == 3 and x.shape[3] == x.shape[4] and x.numel() > 0,
+             f"{what}: x must be a contiguous fp32 [nb, 3, T, S, S] tensor")
+    nb, _, T, S, _ = x.shape
+    _require(isinstance(patch, int) and patch >= 1 and S % patch == 0, f"{what}: clips of {S} pixels are no whole patches of {patch!r}")
+    a = PathClipsArgs()
+    if alpha is not None:
+        _require(samples is None, f"{what}: samples goes with sigma")
+        al = _float_list(f"{what}: alpha", alpha, 1, PATH_MAX_STEPS)
+        _require(all(0.0 <= v <= 1.0 for v in al), f"{what}: alpha must lie in [0, 1], got {al}")
+        kind, m, a.mode = _clip_baseline(what, x, baseline), len(al), PATH_LINE
+        for k, v in enumerate(al):
+            a.alpha[k], a.beta[k] = v, 1.0 - v           # (ctypes rounds the doubles to fp32)
+    else:
+        _require(baseline is None, f"{what}: a baseline goes with alpha")
+        _require(isinstance(samples, int) and not isinstance(samples, bool) and 1 <= samples <= PATH_MAX_STEPS,
+                 f"{what}: samples must be an int in [1, {PATH_MAX_STEPS}], got {samples!r}")
+        _require(_is_f32(sigma) and tuple(sigma.shape) == (nb,), f"{what}: sigma must be a contiguous fp32 [{nb}] tensor")
+        _require(S % 2 == 0, f"{what}: noise is drawn four floats at a time, an odd size {S} is not supported")
+        _require(isinstance(seed, int) and 0 <= seed < 2 ** 64, f"{what}: seed must be an int in [0, 2^64), got {seed!r}")
+        _require(isinstance(clip0, int) and 0 <= clip0 and clip0 + nb < 2 ** 31, f"{what}: clip0 {clip0!r} with {nb} clips")
+        kind, m, a.mode, a.seed, a.clip0 = BASELINE_ZERO, samples, PATH_NOISE, seed, clip0
+    want = (nb, m, 3, T, S, S)
+    _require(out is None or (_is_f32(out) and tuple(out.shape) == want), f"{what}: out must be a contiguous fp32 {want} tensor")
+    _on_device(what, x, baseline, sigma, out)
+    if x.data_ptr() % 16:
+        x = x.clone()
+    if kind == BASELINE_TENSOR and baseline.data_ptr() % 16:
+        baseline = baseline.clone()
+    if out is None:
+        out = torch.empty(want, dtype=torch.float32, device=x.device)
+    _require(out.data_ptr() % 16 == 0, f"{what}: out must be 16-byte aligned")
+    a.x, a.baseline, a.sigma, a.out = ptr(x), ptr(baseline), ptr(sigma), ptr(out)
+    a.nb, a.T, a.size, a.patch, a.baseline_kind, a.m = nb, T, S, patch, kind, m
+    with torch.cuda.device(x.device):
+        check(load().gava_path_clips(C.byref(a), stream_ptr(x.device)), "gava_path_clips")
+    return out
+
+
+def clip_range(x, rel=1.0):
+    """Per-clip range of the fp32 clips x [nb, 3, T, S, S] (gava_clip_range) -> (min, max, sigma), fp32 [nb] each, sigma =
+    fl(rel * fl(max - min)): SmoothGrad's noise level relative to the clip's range.  Exact; a NaN in a clip makes its three
+    values NaN.  Two launches through a small workspace allocated here, no sync."""
+    import math
+    _require(_is_f32(x) and x.dim() == 5 and x.shape[1] == 3 and x.shape[3] == x.shape[4] and x.numel() > 0,
+             "clip_range: x must be a contiguous fp32 [nb, 3, T, S, S] tensor")
+    _require(isinstance(rel, (int, float)) and not isinstance(rel, bool) and math.isfinite(rel), f"clip_range: rel must be a finite number, got {rel!r}")
+    nb = x.shape[0]
+    _require(nb <= 65535, f"clip_range: {nb} clips, at most 65535 go in one call")
+    _on_device("clip_range", x)
+    mn, mx, sg = (torch.empty(nb, dtype=torch.float32, device=x.device) for _ in range(3))
+    ws = torch.empty(nb, CLIP_RANGE_PARTS, 2, dtype=torch.float32, device=x.device)
+    a = ClipRangeArgs()
+    a.x, a.min, a.max, a.sigma, a.workspace = ptr(x), ptr(mn), ptr(mx), ptr(sg), ptr(ws)
+    a.nb, a.T, a.size, a.rel = nb, x.shape[2], x.shape[3], float(rel)
+    with torch.cuda.device(x.device):
+        check(load().gava_clip_range(C.byref(a), stream_ptr(x.device)), "gava_clip_range")
+    return mn, mx, sg
+
+
+def unpatchify_path(dpatch, out, *, B, T, size, patch, mode, frame_rows, row_offset, w, x=None, baseline=None):
+    """unpatchify with the weighted sum over the m = len(w) copies of every clip folded in (gava_unpatchify_path): dpatch fp32
+    holds the B*m*T frames of the copies (clip b's copy k is batch index b*m + k), out has B clips.  G_c = sum_k w_k g_c(b*m + k)
+    as a chain of fused multiply-adds in k order, zero weights skipped; w: a host list.  mode PATH_GRAD -> out [B, 3, T, size,
+    size] = G, PATH_ABSMAX / PATH_L2 -> [B, T, size, size], unpatchify's map rules on G; PATH_ATTR -> [B, 3, T, size, size] =
+    (x - x0) * G, PATH_ATTR_SUM / PATH_ATTR_ABS -> [B, T, size, size], its channel sum / sum of magnitudes.  x (the fp32 clips
+    [B, 3, T, size, size]) and baseline (None = zero, fp32 [3] or shaped like x) belong to the ATTR modes only."""
+    what = "unpatchify_path"
+    _require(mode in (PATH_GRAD, PATH_ABSMAX, PATH_L2, PATH_ATTR, PATH_ATTR_SUM, PATH_ATTR_ABS), f"{what}: unknown mode {mode!r}")
+    attr = mode >= PATH_ATTR
+    _require(attr == (x is not None), f"{what}: x goes with the PATH_ATTR modes and with no other")
+    _require(attr or baseline is None, f"{what}: a baseline goes with the PATH_ATTR modes and with no other")
+    for name, t in (("dpatch", dpatch), ("out", out), ("x", x)):
+        _require(t is None or _is_f32(t), f"{what}: {name} must be a contiguous fp32 tensor")
+    wl = _float_list(f"{what}: w", w, 1, PATH_MAX_STEPS)
+    m = len(wl)
+    _require(min(B, T, size, patch) > 0 and size % patch == 0, f"{what}: B={B} T={T} size={size} patch={patch}")
+    n = (size // patch) ** 2
+    _require(dpatch.dim() in (2, 3) and dpatch.numel() == B * m * T * frame_rows * dpatch.shape[-1] and
+             (dpatch.dim() == 2 or dpatch.shape[1] == frame_rows),
+             f"{what}: dpatch {tuple(dpatch.shape)} is not {B} x {m} x {T} frames of {frame_rows} rows")
+    _require(dpatch.shape[-1] >= 3 * patch * patch, f"{what}: rows of {dpatch.shape[-1]} floats hold no {3 * patch * patch} patch columns")
+    _require(0 <= row_offset and row_offset + n <= frame_rows, f"{what}: rows {row_offset} ... {row_offset + n - 1} of a frame of {frame_rows}")
+    clip = (B, 3, T, size, size)
+    want = clip if mode in (PATH_GRAD, PATH_ATTR) else (B, T, size, size)
+    _require(tuple(out.shape) == want, f"{what}: out is {tuple(out.shape)}, this mode writes {want}")
+    _require(x is None or tuple(x.shape) == clip, f"{what}: x is {tuple(x.shape) if x is not None else None}, not {clip}")
+    kind = _clip_baseline(what, x, baseline) if attr else BASELINE_ZERO
+    _on_device(what, dpatch, out, x, baseline)
+    a = UnpatchifyPathArgs()
+    a.dpatch, a.ld, a.x, a.baseline, a.out = ptr(dpatch), dpatch.shape[-1], ptr(x), ptr(baseline), ptr(out)
+    a.B, a.T, a.size, a.patch, a.mode, a.baseline_kind = B, T, size, patch, mode, kind
+    a.frame_rows, a.row_offset, a.m = frame_rows, row_offset, m
+    for k, v in enumerate(wl):
+        a.w[k] = v
+    with torch.cuda.device(out.device):
+        check(load().gava_unpatchify_path(C.byref(a), stream_ptr(out.device)), "gava_unpatchify_path")
+    return out
+
+
+def path_delta(attr, logits, target, *, m, k_lo, k_hi):
+    """The completeness residual of integrated gradients (gava_path_delta).  attr: the signed map fp32 [B, T, S, S]; logits fp32
+    [B * m, C] (row b*m + k, rows contiguous); target int64 [B] device tensor; k_lo / k_hi: the steps that are the baseline and
+    the clip.  -> dict(sum_attr, f_diff, delta), fp32 [B] each: the clip's summed attribution (added in double in a fixed order,
+    rounded once), logits[b*m + k_hi, target] - logits[b*m + k_lo, target], and their difference.  A target outside [0, C)
+    gives NaN for that clip.  One launch, no sync."""
+    what = "path_delta"
+    _require(_is_f32(attr) and attr.dim() == 4 and attr.shape[2] == attr.shape[3] and attr.numel() > 0,
+             f"{what}: attr must be a contiguous fp32 [B, T, S, S] tensor")
+    B = attr.shape[0]
+    _require(isinstance(m, int) and not isinstance(m, bool) and 1 <= m <= PATH_MAX_STEPS, f"{what}: m must be an int in [1, {PATH_MAX_STEPS}], got {m!r}")
+    _require(torch.is_tensor(logits) and logits.dtype == torch.float32 and logits.dim() == 2 and logits.shape[1] >= 1
+             and (logits.shape[1] == 1 or logits.stride(1) == 1) and logits.stride(0) >= logits.shape[1],
+             f"{what}: logits must be an fp32 [B * m, C] tensor with contiguous rows")
+    _require(logits.shape[0] == B * m, f"{what}: {logits.shape[0]} rows of logits are not {B} clips of {m} steps")
+    for name, k in (("k_lo", k_lo), ("k_hi", k_hi)):
+        _require(isinstance(k, int) and 0 <= k < m, f"{what}: {name} {k!r} is outside the {m} steps")
+    _require(torch.is_tensor(target) and target.dtype == torch.int64 and tuple(target.shape) == (B,) and target.is_contiguous(),
+             f"{what}: target must be a contiguous int64 [{B}] tensor")
+    _on_device(what, attr, logits, target)
+    dev = attr.device
+    res = {k: torch.empty(B, dtype=torch.float32, device=dev) for k in ("sum_attr", "f_diff", "delta")}
+    a = PathDeltaArgs()
+    a.map, a.logits, a.ld, a.target = ptr(attr), ptr(logits), logits.stride(0), ptr(target)
+    a.sum_attr, a.f_diff, a.delta = ptr(res["sum_attr"]), ptr(res["f_diff"]), ptr(res["delta"])
+    a.B, a.T, a.size, a.m, a.C, a.k_lo, a.k_hi = B, attr.shape[1], attr.shape[2], m, logits.shape[1], k_lo, k_hi
+    with torch.cuda.device(dev):
+        check(load().gava_path_delta(C.byref(a), stream_ptr(dev)), "gava_path_delta")
     return res
 
 

@@ -882,6 +882,24 @@ class PerturbationCurves:
         return f"PerturbationCurves(mode={self.mode!r}, " + ", ".join(f"{k}={tuple(getattr(self, k).shape)}" for k in self.__slots__[1:]) + ")"
 
 
+class PathAttribution:
+    """What VitaCLIP.integrated_gradients returns, B clips of T frames as given; device tensors unless said otherwise:
+      maps     fp32 [B, T, S, S] (reduce "sum", "abs", "absmax", "l2") or [B, 3, T, S, S] (reduce=None)
+      logits   [B, C]      the raw logits of x itself (the path's last step)
+      target   [B]         int64: the class each clip was asked about
+      sum_attr [B]         fp32: the clip's summed attribution (None with multiply=False)
+      delta    [B]         fp32: the completeness residual sum_attr - (f(x) - f(x0)) for the target's logit (None with
+                           multiply=False); what is left is the quadrature's error and the bf16 gradient operands'
+      alpha, w [m]         fp32 HOST tensors: the path's points and their weights, zero-weight endpoints included"""
+    __slots__ = ("maps", "logits", "target", "sum_attr", "delta", "alpha", "w")
+
+    def __init__(self, maps, logits, target, sum_attr, delta, alpha, w):
+        self.maps, self.logits, self.target, self.sum_attr, self.delta, self.alpha, self.w = maps, logits, target, sum_attr, delta, alpha, w
+
+    def __repr__(self):
+        return "PathAttribution(" + ", ".join(f"{k}={tuple(getattr(self, k).shape)}" for k in self.__slots__ if getattr(self, k) is not None) + ")"
+
+
 class Faithfulness(dict):
     """What VitaCLIP.faithfulness returns: {method: {"deletion": PerturbationCurves, "insertion": PerturbationCurves}}, the
     methods in the order asked for and the control "random" last.  table() is the text a user reads: per method the mean
@@ -1283,6 +1301,198 @@ class VitaCLIP(nn.Module, _HipHost):
             self.text_features = self.text_features.detach()        # the last reference into this call's graph
         return (dx if mode == hip.UNPATCH_GRAD else request.pop("out")), logits.detach(), target
 
+    _IG_MODES = {(True, "sum"): hip.PATH_ATTR_SUM, (True, "abs"): hip.PATH_ATTR_ABS, (True, None): hip.PATH_ATTR,
+                 (False, None): hip.PATH_GRAD, (False, "absmax"): hip.PATH_ABSMAX, (False, "l2"): hip.PATH_L2}
+    _SMOOTH_MODES = {None: hip.PATH_GRAD, "absmax": hip.PATH_ABSMAX, "l2": hip.PATH_L2}
+
+    def _path_checks(self, what, x, target, m, max_clips, baseline="zero", noise=False):
+        """The refusals integrated_gradients and smooth_grad share, the device's last -> (B, T, clips per chunk)."""
+        S = self._shape["size"]
+        if not (torch.is_tensor(x) and x.dim() == 5 and x.is_floating_point() and x.shape[1] == 3 and x.shape[3] == x.shape[4] == S
+                and x.shape[0] > 0 and x.shape[2] > 0):
+            raise hip.GavaError(f"{what} takes a floating-point clip batch [B, 3, T, {S}, {S}], got "
+                                f"{(x.dtype, tuple(x.shape)) if torch.is_tensor(x) else type(x)}")
+        B, T = x.shape[0], x.shape[2]
+        if self.use_text_prompt_learning and self.prompt_learner.n_kv is None:
+            raise hip.GavaError(f"{what}: a per-descriptor (use_descriptor / desc_wise) head has no single logit per class to differentiate")
+        n_cls = self.prompt_learner.n_cls if self.use_text_prompt_learning else self.text_features.shape[0]
+        if target is not None and not torch.is_tensor(target):
+            if not 0 <= int(target) < n_cls:
+                raise hip.GavaError(f"{what}: target {target} is outside the {n_cls} classes")
+        elif target is not None and not (target.dtype == torch.int64 and tuple(target.shape) == (B,)):
+            raise hip.GavaError(f"{what}: a tensor target must be int64 [{B}] on the device")
+        if isinstance(max_clips, bool) or not isinstance(max_clips, int) or max_clips < 1:
+            raise hip.GavaError(f"{what}: max_clips must be an int >= 1, got {max_clips!r}")
+        if m * T > hip.MAX_GRID_FRAMES:
+            raise hip.GavaError(f"{what}: one clip's {m} copies x {T} frames are past the {hip.MAX_GRID_FRAMES} frames one launch covers")
+        if noise and S % 2:
+            raise hip.GavaError(f"{what}: noise is drawn four floats at a time, an odd size {S} is not supported")
+        kind = baseline if isinstance(baseline, str) else "tensor"
+        if kind not in ("zero", "blur", "tensor") or (kind == "tensor" and not (
+                torch.is_tensor(baseline) and baseline.is_floating_point() and (tuple(baseline.shape) == (3,) or baseline.shape == x.shape))):
+            raise hip.GavaError(f"{what}: baseline must be 'zero', 'blur', a floating-point tensor [3] or one shaped like x, got "
+                                f"{(baseline.dtype, tuple(baseline.shape)) if torch.is_tensor(baseline) else baseline!r}")
+        if not x.is_cuda or (torch.is_tensor(target) and not target.is_cuda):
+            raise hip.GavaError("VitaCLIP (gava_clip_amd) runs on the HIP device only: move the model and the "
+                                "input with .cuda(); there is no CPU fallback")
+        return B, T, max(1, min(max_clips, hip.MAX_GRID_FRAMES // T) // m)
+
+    def _path_maps(self, x, make_copies, mode, w, target, ref_step, step, base=None, signed=None):
+        """The body integrated_gradients and smooth_grad share: `step` clips at a time, make_copies(i, nb) -> the m = len(w)
+        copies of clips [i, i + nb), fp32 [nb, m, 3, T, S, S]; the grad-enabled forward of the nb * m clips; the vision tower's
+        backward with the path request, whose fold (gava_unpatchify_path) reduces each clip's m gradients with the weights w
+        straight into the chunk's slice of the result.  target: int64 [B] or None - then the top-1 class of each clip's copy
+        ref_step, picked on the device.  base: the baseline of the ATTR modes (None, [3] or shaped like x); signed: an fp32
+        [B, T, S, S] tensor that also receives the PATH_ATTR_SUM map (a second fold of the same patch gradients).
+        -> (maps, logits fp32 [B * m, C], target int64 [B])."""
+        B, _, T, S, _ = x.shape
+        m = len(w)
+        attr = mode >= hip.PATH_ATTR
+        shape = (B, 3, T, S, S) if mode in (hip.PATH_GRAD, hip.PATH_ATTR) else (B, T, S, S)
+        maps = torch.empty(shape, dtype=torch.float32, device=x.device)
+        aligned = lambda t: t if t.data_ptr() % 16 == 0 else t.clone()        # (a slice of clips of an odd size)
+        logits, targets = None, []
+        for i in range(0, B, step):
+            nb = min(step, B - i)
+            dst = [maps[i:i + nb]] + ([signed[i:i + nb]] if signed is not None else [])
+            out = [d if d.data_ptr() % 16 == 0 else torch.empty_like(d) for d in dst]
+            b = base[i:i + nb] if base is not None and base.dim() == 5 else base
+            request = dict(mode=mode, m=m, w=w, out=out[0], signed=out[1] if signed is not None else None,
+                           x=aligned(x[i:i + nb]) if attr else None,
+                           baseline=(aligned(b) if b is not None and b.dim() == 5 else b) if attr else None)
+            tg = target[i:i + nb] if target is not None else None
+            with torch.enable_grad():
+                xg = make_copies(i, nb).view(nb * m, 3, T, S, S).requires_grad_()       # a leaf of this call's own
+                lg = self._forward_impl(xg, None, None, False, input_request=request)[0]
+                if tg is None:
+                    tg = lg.detach().view(nb, m, -1)[:, ref_step].argmax(dim=1)
+                score = lg.gather(1, tg.repeat_interleave(m).view(-1, 1)).sum()
+                torch.autograd.grad(score, [xg], allow_unused=True)      # runs the vision tower's backward, nothing else
+            for d, o in zip(dst, out):
+                if o is not d:
+                    d.copy_(o)
+            request.clear()
+            lg = lg.detach()
+            if nb == B:
+                logits = lg
+            else:
+                if logits is None:
+                    logits = torch.empty(B * m, lg.shape[-1], dtype=torch.float32, device=x.device)
+                logits[i * m:(i + nb) * m] = lg
+            targets.append(tg)
+            del xg, score, lg
+        if torch.is_tensor(self.text_features) and self.text_features.requires_grad:
+            self.text_features = self.text_features.detach()        # the last reference into this call's graph
+        return maps, logits, (target if target is not None else targets[0] if len(targets) == 1 else torch.cat(targets, 0))
+
+    def integrated_gradients(self, x, target=None, baseline="zero", steps=16, rule="trapezoid", reduce="sum", multiply=True,
+                             blur_sigma=5.0, max_clips=64):
+        """Integrated gradients (Sundararajan et al., "Axiomatic Attribution for Deep Networks") of a class's raw logit along
+        the straight path from a baseline x0 to the clip -> PathAttribution (see there for the fields):
+          a = (x - x0) * sum_k w_k  d logit_target / d x (x0 + alpha_k (x - x0))
+        The one map here with a checkable axiom: a clip's attributions sum to f(x) - f(x0) up to the quadrature's error, and
+        .delta is that residual (what Captum calls the convergence delta).
+          reduce="sum"  [B, T, S, S]  a_0 + a_1 + a_2, signed: what speaks FOR the class is positive
+          reduce="abs"  [B, T, S, S]  |a_0| + |a_1| + |a_2|
+          reduce=None   [B, 3, T, S, S]  a itself
+        multiply=False returns the path-mean gradient G = sum_k w_k grad_k instead; reduce is then None ([B, 3, T, S, S]),
+        "absmax" or "l2" (saliency's map rules on G), and sum_attr / delta are None.
+        baseline: as for perturbation_curves - "zero", "blur" (blur_sigma), an fp32 tensor [3] or one shaped like x.
+        rule="trapezoid": m = steps >= 2 points alpha_k = k / (m - 1), end weights halved; x0 and x are steps 0 and m - 1, so
+        f(x0) and f(x) come with the path.  rule="gausslegendre": the `steps` Gauss-Legendre nodes on [0, 1] - exact for
+        polynomials of degree 2 steps - 1, where the trapezoid's error falls as 1 / m^2 - plus the two endpoints as zero-weight
+        steps (m = steps + 2): their forwards and backwards add nothing to the map and are the price of the residual.
+        target: None - the top-1 class of the clip itself, the alpha = 1 row of the same forward, picked on the device -, an
+        int (checked on the host) or an int64 [B] device tensor (not range-checked; out of range: NaN sum_attr and delta).
+        The m copies of a clip are written by one kernel (gava_path_clips), go through the grad-enabled forward and the
+        vision tower's backward as a batch, and the fold reduces their m patch gradients into the clip's one map
+        (gava_unpatchify_path): the m full-size gradients are never in memory.  max(1, max_clips // m) whole clips run at a
+        time; a chunk's copies (4.8 MB each at 224 px and T = 8) and kept activations are in memory at once.
+        Works in eval() and train() mode and under no_grad (the call enables grad for itself); no parameter's .grad is
+        touched, nothing survives the call, nothing waits for the device.  A per-descriptor head is refused."""
+        what = "integrated_gradients"
+        if (bool(multiply), reduce) not in self._IG_MODES:
+            raise hip.GavaError(f"{what}: reduce must be 'sum', 'abs' or None (multiply=False: None, 'absmax' or 'l2'), got {reduce!r}")
+        mode = self._IG_MODES[(bool(multiply), reduce)]
+        alpha, w = hip.path_rule(rule, steps)
+        m = len(alpha)
+        kind = baseline if isinstance(baseline, str) else "tensor"
+        taps = hip.gaussian_taps(blur_sigma) if kind == "blur" else None
+        B, T, step = self._path_checks(what, x, target, m, max_clips, baseline=baseline)
+        dev, P = x.device, self._shape["P"]
+        with torch.cuda.device(dev):
+            x = x.detach().float().contiguous()
+            if kind == "zero":
+                base = None
+            elif kind == "blur":
+                # the few dozen taps go up from pinned memory on the stream: a pageable copy would be the call's one host wait
+                base = hip.blur_clips(x, taps.pin_memory().to(dev, non_blocking=True))
+            else:
+                base = baseline.detach().to(dev).float().contiguous()
+            if target is not None and not torch.is_tensor(target):
+                target = torch.full((B,), int(target), dtype=torch.int64, device=dev)
+            copies = lambda i, nb: hip.path_clips(x[i:i + nb], patch=P, alpha=alpha,
+                                                  baseline=base[i:i + nb] if base is not None and base.dim() == 5 else base)
+            signed = None
+            if multiply and reduce != "sum":
+                signed = torch.empty(B, T, x.shape[3], x.shape[4], dtype=torch.float32, device=dev)
+            maps, logits, target = self._path_maps(x, copies, mode, w, target, m - 1, step, base=base, signed=signed)
+            sum_attr = delta = None
+            if multiply:
+                d = hip.path_delta(maps if signed is None else signed, logits, target.contiguous(), m=m, k_lo=0, k_hi=m - 1)
+                sum_attr, delta = d["sum_attr"], d["delta"]
+            logits = logits.view(B, m, -1)[:, m - 1].contiguous()
+        return PathAttribution(maps, logits, target, sum_attr, delta, torch.tensor(alpha, dtype=torch.float32), torch.tensor(w, dtype=torch.float32))
+
+    def smooth_grad(self, x, target=None, samples=16, sigma=0.15, relative=True, seed=0, reduce="absmax", max_clips=64):
+        """SmoothGrad (Smilkov et al., "SmoothGrad: removing noise by adding noise"): the mean over `samples` noisy copies
+        x + sigma_b z, z ~ N(0, 1), of the gradient saliency() takes -> (maps, logits [B, C] of x itself, target int64 [B]),
+        like saliency; maps is fp32 [B, T, S, S] (reduce="absmax" / "l2", saliency's map rules on the MEAN gradient) or the mean
+        gradient itself, [B, 3, T, S, S] (reduce=None).
+        sigma: with relative=True the noise level as a share of each clip's own max - min (gava_clip_range; the paper's 10-20 %),
+        else absolute, in the normalised space clips live in.  The noise is counter-based (Philox4x32-10 keyed by `seed`,
+        counted by clip, sample and element - gava_path_clips): a call repeats bit for bit, and neither the batch a clip
+        arrives in nor max_clips changes its noise.  A clip that holds a NaN gets a NaN map.
+        target: None - the top-1 class of x itself - an int or an int64 [B] device tensor, as for saliency.  The plain no-grad
+        forward of x that gives `logits` (and that target) runs in every case, max_clips clips at a time (it keeps no
+        activations).  Chunks, memory and the guarantees are
+        integrated_gradients': max(1, max_clips // samples) clips at a time, the fold (gava_unpatchify_path) averages the
+        copies' patch gradients on the way, no .grad is touched, nothing waits for the device."""
+        what = "smooth_grad"
+        if reduce not in self._SMOOTH_MODES:
+            raise hip.GavaError(f"{what}: reduce must be 'absmax', 'l2' or None, got {reduce!r}")
+        if isinstance(samples, bool) or not isinstance(samples, int) or not 1 <= samples <= hip.PATH_MAX_STEPS:
+            raise hip.GavaError(f"{what}: samples must be an int in [1, {hip.PATH_MAX_STEPS}], got {samples!r}")
+        if isinstance(sigma, bool) or not isinstance(sigma, (int, float)) or not (math.isfinite(sigma) and sigma >= 0):
+            raise hip.GavaError(f"{what}: sigma must be a finite number >= 0, got {sigma!r}")
+        if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
+            raise hip.GavaError(f"{what}: seed must be an int in [0, 2^64), got {seed!r}")
+        m = samples
+        B, T, step = self._path_checks(what, x, target, m, max_clips, noise=True)
+        dev, P = x.device, self._shape["P"]
+        with torch.cuda.device(dev):
+            x = x.detach().float().contiguous()
+            plain = min(max_clips, hip.MAX_GRID_FRAMES // T)        # the plain forward keeps nothing: max_clips clips at a time
+            with torch.no_grad():
+                logits = None
+                for i in range(0, B, plain):
+                    lg = self.local_logits(self._forward_impl(x[i:i + plain], None, None, False)[0])
+                    if lg.shape[0] == B:
+                        logits = lg
+                        break
+                    if logits is None:
+                        logits = torch.empty(B, lg.shape[-1], dtype=torch.float32, device=dev)
+                    logits[i:i + plain] = lg
+                self.last["local_batch"] = B
+            if target is None:
+                target = logits.argmax(dim=1)
+            elif not torch.is_tensor(target):
+                target = torch.full((B,), int(target), dtype=torch.int64, device=dev)
+            sg = hip.clip_range(x, float(sigma))[2] if relative else torch.full((B,), float(sigma), dtype=torch.float32, device=dev)
+            copies = lambda i, nb: hip.path_clips(x[i:i + nb], patch=P, sigma=sg[i:i + nb], samples=m, seed=seed, clip0=i)
+            maps, _, _ = self._path_maps(x, copies, self._SMOOTH_MODES[reduce], [1.0 / m] * m, target, 0, step)
+        return maps, logits, target
+
     def attention_maps(self, x, mode="rollout", layer=-1, heads="mean", max_clips=None):
         """What the CLS token of every frame attends to -> AttentionMaps (see there for the fields).
           mode="rollout"  attention rollout of the CLS token through all blocks: row 0 of A^_L ... A^_1, A^_l = (I + mean_h
@@ -1572,13 +1782,15 @@ class VitaCLIP(nn.Module, _HipHost):
         return PerturbationCurves(mode, torch.tensor(fr, dtype=torch.float32), res["logit"], res["prob"], res["top1"],
                                   res["auc_logit"], res["auc_prob"], res["target"], ranks)
 
-    _FAITHFULNESS_METHODS = ("rollout", "relevance", "saliency")
+    _FAITHFULNESS_METHODS = ("rollout", "relevance", "saliency", "integrated", "smoothgrad")
 
     def faithfulness(self, x, methods=("rollout", "relevance", "saliency"), target=None, seed=0, **kw):
         """Which map to believe for this model and these clips: both perturbation curves of every method's map, for one and
         the same target, next to a random ranking -> Faithfulness, {name: {"deletion": ..., "insertion": ...}}; print its
         .table().  methods: any of "rollout" (attention_maps(x).patches), "relevance" (relevance_maps(x, target).patches) and
-        "saliency" (saliency(x, target)[0], pixels pooled to patches); the control "random" ranks by uniform scores drawn from
+        "saliency" (saliency(x, target)[0], pixels pooled to patches), and on request "integrated"
+        (integrated_gradients(x, target).maps, the signed sum: what speaks FOR the class goes first, as with relevance) and
+        "smoothgrad" (smooth_grad(x, target)[0]), both with their defaults; the control "random" ranks by uniform scores drawn from
         a device generator seeded with `seed`, so a call repeats bit for bit.  target: as for perturbation_curves; None is the
         top-1 class of the plain forward of x, picked on the device once and used for every method.  **kw goes to
         perturbation_curves (steps, fractions, scope, baseline, blur_sigma, max_clips; not mode).  Evaluation only, like
@@ -1608,6 +1820,10 @@ class VitaCLIP(nn.Module, _HipHost):
                     maps[m] = self.attention_maps(x).patches
                 elif m == "relevance":
                     maps[m] = self.relevance_maps(x, target).patches
+                elif m == "integrated":
+                    maps[m] = self.integrated_gradients(x, target).maps
+                elif m == "smoothgrad":
+                    maps[m] = self.smooth_grad(x, target)[0]
                 else:
                     maps[m] = self.saliency(x, target)[0]
             gen = torch.Generator(device=x.device)

@@ -25,7 +25,9 @@ VitaCLIP_vision_encoder_utils.py:155-203 in reverse as a list of stages, on scra
                LN1' of the main rows
     _embedding_backward  ln_pre', sum over tokens = d time_embed
     _input_backward      only when d x is asked for: patch projection^T (dgrad GEMM), then the fold of the patch rows back into
-                         the clip (gava_unpatchify) - the gradient itself, or a saliency map of it without the gradient in memory
+                         the clip (gava_unpatchify) - the gradient itself, or a saliency map of it without the gradient in memory;
+                         with a path request (VitaCLIP.integrated_gradients / smooth_grad) the fold also reduces the m copies of
+                         every clip to one map (gava_unpatchify_path)
     _relevance_step      only with a relevance request (VitaCLIP.relevance_maps): per block, right after its d mix exists, one step of
                          the gradient-weighted attention relevance chain (gava_attention_relevance); the backward ends after block 0's
 The second half of the module is the step's tail: similarity head and criterion on the device.
@@ -441,16 +443,25 @@ def _embedding_backward(model, d, e0, dX, dx16=None):
     return dte
 
 
-def _input_backward(model, bw, d, dx16, mode, x=None):
+def _input_backward(model, bw, d, dx16, mode, x=None, path=None):
     """d(embedding output) -> d x (VitaCLIP_vision_encoder_utils.py:31-53 in reverse).  dx16 [R, D]: the bf16 copy of dX after
     ln_pre', all B_in*T_in*(n+1) rows in (b, t_in) order.  The embedding is patches @ Wp^T plus terms that do not depend on x
     (conv bias, pos_embed, time_embed, the cls_token rows), so d patches = dX @ Wp - one dgrad GEMM over every row, the CLS
     rows included (1/(n+1) of the work, and no gather) - and gava_unpatchify folds the patch rows back into the clip, skipping
     each frame's CLS row.  mode: hip.UNPATCH_*; GRAD -> fp32 [B_in, 3, T_in, size, size], the map modes -> [B_in, T_in, size,
-    size] (x: the fp32 clip, UNPATCH_GRAD_X_INPUT only).  The product lives for this call only."""
+    size] (x: the fp32 clip, UNPATCH_GRAD_X_INPUT only).  The product lives for this call only.
+    path: the path request of VitaCLIP.integrated_gradients / smooth_grad - the B_in clips are m copies each of B_in / m clips,
+    mode is hip.PATH_* and the fold reduces the copies with the weights w as it goes (gava_unpatchify_path), into path["out"]:
+    one map per ORIGINAL clip, the m gradients are never formed."""
     sh, w = model._shape, bw["w_patch_t"]
     dpatch = new(d.dev, d.R, w.shape[0], dtype=torch.float32)
     hip.gemm(dx16, w, None, dpatch, epilogue=hip.EPI_F32, prec=BWD)
+    if path is not None:
+        geo = dict(B=d.B_in // path["m"], T=d.T_in, size=sh["size"], patch=sh["P"], frame_rows=d.n1, row_offset=1, w=path["w"], x=x,
+                   baseline=path.get("baseline"))
+        if path.get("signed") is not None:      # the signed map next to an unsigned one: a second fold of the same rows
+            hip.unpatchify_path(dpatch, path["signed"], mode=hip.PATH_ATTR_SUM, **geo)
+        return hip.unpatchify_path(dpatch, path["out"], mode=mode, **geo)
     shape = (d.B_in, 3, d.T_in) if mode == hip.UNPATCH_GRAD else (d.B_in, d.T_in)
     out = new(d.dev, *shape, sh["size"], sh["size"], dtype=torch.float32)
     return hip.unpatchify(dpatch, out, B=d.B_in, T=d.T_in, size=sh["size"], patch=sh["P"], mode=mode, frame_rows=d.n1, row_offset=1, x=x)
@@ -502,7 +513,8 @@ def vision_backward(model, saved, dcls_x, B, T, dsummary=None, kept=None, input_
     grads["global_prompts"] = dgp
     grads["time_embed"] = _embedding_backward(model, d, e0, dX, dx16=s.dx16 if input_grad is not None else None)
     if input_grad is not None:
-        grads["input"] = _input_backward(model, bw, d, s.dx16, input_grad["mode"], input_grad.get("x"))
+        grads["input"] = _input_backward(model, bw, d, s.dx16, input_grad["mode"], input_grad.get("x"),
+                                         path=input_grad if "m" in input_grad else None)
     return grads
 
 
@@ -517,7 +529,9 @@ class VisionTowerFn(torch.autograd.Function):
     VitaCLIP.saliency - mode (hip.UNPATCH_*) and x; a map mode's result is left in request["out"] instead of being returned
     (it has not x's shape), so that the full-size gradient is never formed.  Or the dict of VitaCLIP.relevance_maps,
     dict(relevance=state): the backward then runs the relevance chain beside the gradient, leaves r in request["out"] and
-    returns no gradient at all."""
+    returns no gradient at all.  Or the path form of VitaCLIP.integrated_gradients / smooth_grad, dict(mode=hip.PATH_*, m, w,
+    x, baseline, out, signed): x holds m copies of every clip, the fold reduces them with the weights w (gava_unpatchify_path) into the
+    tensor the caller put in request["out"], and no gradient is returned either."""
 
     @staticmethod
     def forward(fctx, model, x, clips, request, *params):
@@ -551,7 +565,7 @@ class VisionTowerFn(torch.autograd.Function):
         dx = g.get("input")
         if "relevance" in g:
             req["out"] = g["relevance"]
-        if dx is not None and req["mode"] != hip.UNPATCH_GRAD:
+        if dx is not None and (req["mode"] != hip.UNPATCH_GRAD or "m" in req):      # a map, or a path request's reduced result
             req["out"], dx = dx, None
         out = []
         for name, p in model._vision_trainables():

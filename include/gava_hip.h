@@ -992,6 +992,117 @@ int gava_perturb_scores(const gava_perturb_scores_args* a, gava_stream_t stream)
  * like gava_attention_relevance_struct_sizes.  Writes min(cap, 4) entries, returns 4. */
 int gava_perturbation_struct_sizes(size_t* out, int cap);
 
+/* ---- path gradients: integrated gradients and SmoothGrad, accumulated in the fold -------------------------------------------
+ *
+ * Both repairs of the plain pixel gradient are m gradients of near-copies of a clip reduced to one map: integrated gradients
+ * (Sundararajan et al.) (x - x0) * sum_k w_k df/dx(x0 + alpha_k (x - x0)) along the straight path from a baseline x0, SmoothGrad
+ * (Smilkov et al.) the mean gradient over m noisy copies.  gava_path_clips writes the m copies of every clip, the forward and
+ * the backward run on the nb * m clips as on any batch, gava_unpatchify_path folds the patch gradients of a clip's m copies
+ * into ONE map - the m full-size gradients are never in memory -, gava_path_delta is the completeness residual
+ * sum(attributions) - (f(x) - f(x0)), and gava_clip_range gives the noise its scale.  None of the four uses an atomic: a call
+ * repeats bit for bit.  Offsets are 64-bit.  One launch each on `stream`, except gava_clip_range (two).  The vector width is
+ * gava_unpatchify's and gava_perturb_clips': 16 bytes per lane when patch is a multiple of 4 (the fold: and ld too), 8 when
+ * they are even (P = 14), single floats otherwise.
+ *
+ * gava_path_clips.  x fp32 [nb][3][T][size][size] -> out fp32 [nb][m][3][T][size][size]; x (and a tensor baseline) is read
+ * once and written m times.
+ *   GAVA_PATH_LINE   out[b][k] = fma(alpha[k], x, beta[k] * x0): one rounded product, one fused multiply-add.  alpha, beta:
+ *                    fp32 by value, beta = 1 - alpha formed by the caller (in double, then rounded); alpha = 0, beta = 1 gives
+ *                    x0 and alpha = 1, beta = 0 gives x, value for value.  x0: GAVA_BASELINE_ZERO (+0.0f), _CHANNEL (baseline =
+ *                    DEVICE fp32 [3]) or _TENSOR (baseline fp32 shaped like x).  sigma must be NULL.
+ *   GAVA_PATH_NOISE  out[b][k] = fma(sigma[b], z, x), sigma DEVICE fp32 [nb], z a standard normal that depends on (seed,
+ *                    clip0 + b, k, the element's index within the clip) and on nothing else - not on nb, not on how the clips
+ *                    are cut into calls, not on the launch.  Philox4x32-10 with key (seed's low word, seed's high word) and
+ *                    counter (e4's low word, e4's high word, k, clip0 + b), e4 = the index of a group of four consecutive
+ *                    floats of the clip; its output words r0..r3 give the group's four normals by two Box-Muller pairs:
+ *                    u1 = ((r0 >> 8) + 1) * 2^-24, u2 = (r1 >> 8) * 2^-24, z0 = sqrtf(-2 logf(u1)) * cosf(2 pi u2), z1 the
+ *                    same with sinf; r2, r3 give z2, z3 the same way.  clip0: the global index of this call's first clip.
+ *                    size must be even (3*T*size*size is then a multiple of 4); baseline NULL, kind GAVA_BASELINE_ZERO.
+ * GAVA_EINVAL: null args / x / out, a baseline pointer that does not go with the kind (or any in noise mode), nb, T, size,
+ * patch < 1 or size % patch != 0, m outside [1, GAVA_PATH_MAX_STEPS], an unknown mode or kind, x / out / a tensor baseline
+ * not 16-byte aligned, line mode: sigma given, an alpha or beta outside [0, 1] or not finite; noise mode: sigma missing, an
+ * odd size, clip0 < 0 or clip0 + nb past 2^31 - 1.
+ *
+ * gava_clip_range.  x fp32 [nb][3][T][size][size] -> min[b], max[b] over the whole clip and sigma[b] = fl(rel * fl(max - min)),
+ * DEVICE fp32 [nb] each.  Two launches: GAVA_CLIP_RANGE_PARTS workgroups per clip leave their partial results in workspace
+ * (fp32, nb * GAVA_CLIP_RANGE_PARTS * 2 floats), one workgroup per clip finishes.  Exact (min and max do not depend on the
+ * order).  A NaN propagates: a clip that holds one gets min = max = sigma = NaN, and so do its noisy copies and their map.
+ * GAVA_EINVAL: a null pointer, nb, T or size < 1, nb > 65535, a pointer that is not 4-byte aligned.
+ *
+ * gava_unpatchify_path.  gava_unpatchify's geometry and argument checks (dpatch, ld, frame_rows, row_offset, size, patch as
+ * there), with one difference: out has B clips while dpatch holds the frames of B*m - clip b's copies are batch indices
+ * b*m + k, k in [0, m) - and they are reduced while folding.  With g_c(j) gava_unpatchify's g of batch index j,
+ *   G_c = sum_k w[k] * g_c(b*m + k)
+ * as the chain G <- fma(w[k], g, G) over k = 0 ... m-1 from +0.0f; steps with w[k] == 0 are skipped (their rows are not read).
+ * w: fp32 by value.
+ *   GAVA_PATH_GRAD      out fp32 [B][3][T][size][size] = G
+ *   GAVA_PATH_ABSMAX    out fp32 [B][T][size][size]    = max over c of |G_c|
+ *   GAVA_PATH_L2        out                            = sqrt(G_0^2 + G_1^2 + G_2^2), as GAVA_UNPATCH_L2 forms it
+ *   GAVA_PATH_ATTR      out fp32 [B][3][T][size][size] = a_c = fl(fl(x_c - x0_c) * G_c)
+ *   GAVA_PATH_ATTR_SUM  out fp32 [B][T][size][size]    = (a_0 + a_1) + a_2
+ *   GAVA_PATH_ATTR_ABS  out                            = (|a_0| + |a_1|) + |a_2|
+ * x: the fp32 clips [B][3][T][size][size]; x0 by baseline_kind as for gava_path_clips.  Both belong to the three ATTR modes
+ * and are refused in the others (baseline NULL, kind GAVA_BASELINE_ZERO there).  With m = 1 and w = {1} the first three modes
+ * give gava_unpatchify's values.  One workgroup owns P image rows of a frame of the OUTPUT: it reads m times 12 B per pixel
+ * and writes 4 or 12.  GAVA_EINVAL: gava_unpatchify's list (B*T*m in place of B*T), m outside [1, GAVA_PATH_MAX_STEPS], a
+ * weight that is not finite, an unknown mode or kind, x missing in an ATTR mode, x or a baseline given in another, a baseline
+ * pointer that does not go with the kind, x / a tensor baseline not 16-byte aligned.
+ *
+ * gava_path_delta.  map: the signed attribution map fp32 [B][T][size][size] (GAVA_PATH_ATTR_SUM); logits fp32, B*m rows of C
+ * (row b*m + k, rows ld floats apart); target DEVICE int64 [B].  Per clip, DEVICE fp32 [B] each:
+ *   sum_attr = the sum of the clip's map, f_diff = fl(logits[b*m + k_hi][target] - logits[b*m + k_lo][target]),
+ *   delta = fl(sum_attr - f_diff)
+ * (k_lo: the step that is x0, k_hi: the step that is x).  One workgroup of 256 threads per clip; the sum runs in double in a
+ * fixed order - thread i adds elements i, i + 256, ... in that order, a fixed xor butterfly over the lanes of a wave, then the
+ * four waves in order - and is rounded to fp32 once.  A target outside [0, C) is not read through: that clip's three outputs
+ * are NaN.  GAVA_EINVAL: a null pointer, B, T, size or C < 1, ld < C, m outside [1, GAVA_PATH_MAX_STEPS], k_lo or k_hi
+ * outside [0, m), a misaligned pointer. */
+#define GAVA_PATH_MAX_STEPS 64
+#define GAVA_CLIP_RANGE_PARTS 64
+#define GAVA_PATH_LINE 0
+#define GAVA_PATH_NOISE 1
+#define GAVA_PATH_GRAD 0
+#define GAVA_PATH_ABSMAX 1
+#define GAVA_PATH_L2 2
+#define GAVA_PATH_ATTR 3
+#define GAVA_PATH_ATTR_SUM 4
+#define GAVA_PATH_ATTR_ABS 5
+typedef struct {
+  const float* x; const float* baseline; const float* sigma; float* out;
+  int nb, T, size, patch, mode, baseline_kind, m, clip0;
+  uint64_t seed;
+  float alpha[GAVA_PATH_MAX_STEPS]; float beta[GAVA_PATH_MAX_STEPS];
+} gava_path_clips_args;
+int gava_path_clips(const gava_path_clips_args* a, gava_stream_t stream);
+
+typedef struct {
+  const float* x; float* min; float* max; float* sigma;
+  float* workspace;                            /* fp32 [nb][GAVA_CLIP_RANGE_PARTS][2] */
+  int nb, T, size; float rel;
+} gava_clip_range_args;
+int gava_clip_range(const gava_clip_range_args* a, gava_stream_t stream);
+
+typedef struct {
+  const float* dpatch; int64_t ld;
+  const float* x; const float* baseline;       /* the ATTR modes only, NULL otherwise */
+  float* out;
+  int B, T, size, patch, mode, baseline_kind, frame_rows, row_offset, m, reserved;
+  float w[GAVA_PATH_MAX_STEPS];
+} gava_unpatchify_path_args;
+int gava_unpatchify_path(const gava_unpatchify_path_args* a, gava_stream_t stream);
+
+typedef struct {
+  const float* map; const float* logits; int64_t ld;
+  const int64_t* target;                       /* DEVICE [B] */
+  float* sum_attr; float* f_diff; float* delta;        /* [B] */
+  int B, T, size, m, C, k_lo, k_hi, reserved;
+} gava_path_delta_args;
+int gava_path_delta(const gava_path_delta_args* a, gava_stream_t stream);
+
+/* sizeof of gava_path_clips_args, gava_clip_range_args, gava_unpatchify_path_args, gava_path_delta_args, in that order, like
+ * gava_perturbation_struct_sizes.  Writes min(cap, 4) entries, returns 4. */
+int gava_path_grad_struct_sizes(size_t* out, int cap);
+
 /* sizeof of every ABI struct as the library was compiled, in the order gemm_args, layernorm_args, attention_args,
  * attention_f32_args, clip_desc, vision_layer, vision_layer8, vision_model, text_layer, text_model, layernorm_bwd_args,
  * attention_bwd_args, vision_saved, preprocess_args, patchify_args, preprocess_clips_args, view_scores_args.  Writes
