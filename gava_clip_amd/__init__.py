@@ -19,6 +19,9 @@ def __getattr__(name):  # lazy: importing the package must not need torch/HIP
     if name == "TrainCriterion":
         from .training import TrainCriterion
         return TrainCriterion
+    if name in ("ClipMixer", "SoftTargetCriterion"):
+        from . import training
+        return getattr(training, name)
     if name == "AuxCriterion":
         from .training import AuxCriterion
         return AuxCriterion

@@ -38,7 +38,8 @@ EXPORTS = ["gava_abi_version", "gava_gemm", "gava_layernorm", "gava_attention",
            "gava_attention_mass", "gava_attention_maps_struct_sizes",
            "gava_attention_relevance", "gava_attention_relevance_struct_sizes",
            "gava_patch_ranks", "gava_blur_clips", "gava_perturb_clips", "gava_perturb_scores", "gava_perturbation_struct_sizes",
-           "gava_path_clips", "gava_clip_range", "gava_unpatchify_path", "gava_path_delta", "gava_path_grad_struct_sizes"]
+           "gava_path_clips", "gava_clip_range", "gava_unpatchify_path", "gava_path_delta", "gava_path_grad_struct_sizes",
+           "gava_mix_clips", "gava_mix_targets", "gava_soft_criterion", "gava_soft_criterion_backward", "gava_mix_struct_sizes"]
 ATTENTION_MASS_MAX_KEYS = 640     # gava_attention_mass keeps K of one (frame, head) resident in LDS
 ATTENTION_RELEVANCE_MAX_KEYS = 640     # and so does gava_attention_relevance
 PERTURB_MAX_UNITS = 65536         # patches or frames one gava_patch_ranks ranking holds
@@ -310,6 +311,28 @@ class PathDeltaArgs(C.Structure):
                 ("k_lo", C.c_int), ("k_hi", C.c_int), ("reserved", C.c_int)]
 
 
+class MixDesc(C.Structure):
+    _fields_ = [("partner", C.c_int32), ("lam", C.c_float), ("y0", C.c_int32), ("y1", C.c_int32), ("x0", C.c_int32), ("x1", C.c_int32)]
+
+
+class MixClipsArgs(C.Structure):
+    _fields_ = [("x", _fp), ("out", _fp), ("desc_host", C.c_void_p), ("desc", _vp),
+                ("B", C.c_int), ("planes", C.c_int), ("H", C.c_int), ("W", C.c_int)]
+
+
+class MixTargetsArgs(C.Structure):
+    _fields_ = [("labels", _ip), ("desc", _vp), ("targets", _fp), ("ld_targets", C.c_int64),
+                ("B", C.c_int), ("C", C.c_int), ("smoothing", C.c_float), ("reserved", C.c_int)]
+
+
+class SoftCriterionArgs(C.Structure):
+    _fields_ = [("logits", _fp), ("ld_logits", C.c_int64), ("targets", _fp), ("ld_targets", C.c_int64),
+                ("B", C.c_int), ("C", C.c_int), ("weighted", C.c_int),
+                ("alpha", C.c_float), ("gamma", C.c_float), ("beta", C.c_float), ("scale", C.c_float),
+                ("loss", _fp), ("per_sample", _fp), ("weight", _fp), ("top1", _ip), ("target1", _ip), ("hits", _ip), ("conf", _ip),
+                ("saved", _fp), ("grad_loss", _fp), ("dlogits", _fp), ("ld_dlogits", C.c_int64)]
+
+
 class VisionSaved(C.Structure):
     _fields_ = [("e0", _fp), ("x", _fp), ("x1", _fp), ("qkv", _vp), ("pre", _vp), ("sidekv", _vp),
                 ("last_q", _vp), ("last_x1", _fp), ("last_pre", _vp)]
@@ -525,6 +548,18 @@ def load():
     if lib.gava_path_grad_struct_sizes(sizes, len(path_mirrors)) != len(path_mirrors):
         raise GavaError("libgava_hip.so and gava_clip_amd/hip.py disagree on the number of path-gradient ABI structs")
     for cls, sz in zip(path_mirrors, sizes):
+        if C.sizeof(cls) != sz:
+            raise GavaError(f"ctypes mirror {cls.__name__} is {C.sizeof(cls)} bytes, the library's struct {sz}: gava_clip_amd/hip.py is out of "
+                            f"step with include/gava_hip.h")
+    # the mix's and the soft-target criterion's structs, the same way
+    mix_mirrors = [MixDesc, MixClipsArgs, MixTargetsArgs, SoftCriterionArgs]
+    for name, cls in (("gava_mix_clips", MixClipsArgs), ("gava_mix_targets", MixTargetsArgs),
+                      ("gava_soft_criterion", SoftCriterionArgs), ("gava_soft_criterion_backward", SoftCriterionArgs)):
+        getattr(lib, name).argtypes, getattr(lib, name).restype = [C.POINTER(cls), _vp], C.c_int
+    lib.gava_mix_struct_sizes.argtypes, lib.gava_mix_struct_sizes.restype = [C.POINTER(C.c_size_t), C.c_int], C.c_int
+    if lib.gava_mix_struct_sizes(sizes, len(mix_mirrors)) != len(mix_mirrors):
+        raise GavaError("libgava_hip.so and gava_clip_amd/hip.py disagree on the number of mix ABI structs")
+    for cls, sz in zip(mix_mirrors, sizes):
         if C.sizeof(cls) != sz:
             raise GavaError(f"ctypes mirror {cls.__name__} is {C.sizeof(cls)} bytes, the library's struct {sz}: gava_clip_amd/hip.py is out of "
                             f"step with include/gava_hip.h")
@@ -1369,6 +1404,119 @@ def train_criterion_backward(logits, labels, saved, grad_loss):
     a.B, a.C, a.saved, a.grad_loss, a.dlogits, a.ld_dlogits = B, Cn, ptr(saved), ptr(grad_loss), ptr(dlogits), Cn
     with torch.cuda.device(logits.device):
         check(load().gava_train_criterion_backward(C.byref(a), stream_ptr(logits.device)), "gava_train_criterion_backward")
+    return dlogits
+
+
+# ---- Mixup / CutMix and the criterion for soft targets (gava_mix_*, gava_soft_criterion*) ---------------------------------------
+
+def mix_descriptors(plan, H, W, device=None):
+    """The host plan of a mix - dict(partner int [B], lam float [B], box int [B, 4] as (y0, y1, x0, x1)) - as the ABI's
+    descriptor table, twice: -> dict(host = pinned uint8 tensor holding B gava_mix_desc (what gava_mix_clips validates),
+    dev = its device copy (what the kernels read), B, H, W).  The copy is non-blocking from pinned memory on the current
+    stream; nothing waits for it."""
+    import numpy as np
+    partner = np.ascontiguousarray(plan["partner"], dtype=np.int32).reshape(-1)
+    B = partner.shape[0]
+    lam = np.ascontiguousarray(plan["lam"], dtype=np.float32).reshape(-1)
+    box = np.ascontiguousarray(plan["box"], dtype=np.int32).reshape(-1, 4)
+    _require(lam.shape[0] == B and box.shape[0] == B and B >= 1, "mix_descriptors: partner [B], lam [B] and box [B, 4] must agree")
+    host = torch.empty(B * C.sizeof(MixDesc), dtype=torch.uint8).pin_memory()
+    rows = host.numpy().view(np.int32).reshape(B, 6)
+    rows[:, 0], rows[:, 1], rows[:, 2:] = partner, lam.view(np.int32), box
+    dev = host.to(device if device is not None else torch.device("cuda", torch.cuda.current_device()), non_blocking=True)
+    return dict(host=host, dev=dev, B=B, H=int(H), W=int(W))
+
+
+def mix_clips(x, desc, out=None):
+    """Mixup / CutMix of a batch of clips by `desc` (mix_descriptors): gava_mix_clips.  x: contiguous device fp32
+    [B, ..., H, W]; out: None (a new tensor), x itself (in place; the partners must then pair up) or another contiguous
+    tensor of x's shape.  -> out.  The descriptors are validated by the library before any launch."""
+    _on_device("mix_clips", x)
+    _require(_is_f32(x) and x.dim() >= 3 and x.is_contiguous(), "mix_clips: x must be a contiguous fp32 [B, ..., H, W] tensor")
+    B, H, W = x.shape[0], x.shape[-2], x.shape[-1]
+    _require(B >= 1 and x.numel() > 0, "mix_clips: x is empty")
+    _require((desc["B"], desc["H"], desc["W"]) == (B, H, W), "mix_clips: the descriptors were made for another batch or image size")
+    _require(desc["dev"].device == x.device, "mix_clips: the descriptor table is on another device")
+    if out is None:
+        out = torch.empty_like(x)
+    _require(out.is_cuda and out.device == x.device and _is_f32(out) and out.shape == x.shape and out.is_contiguous(),
+             "mix_clips: out must be a contiguous fp32 tensor of x's shape on its device")
+    a = MixClipsArgs()
+    a.x, a.out, a.desc_host, a.desc = ptr(x), ptr(out), desc["host"].data_ptr(), ptr(desc["dev"])
+    a.B, a.planes, a.H, a.W = B, x.numel() // (B * H * W), H, W
+    with torch.cuda.device(x.device):
+        check(load().gava_mix_clips(C.byref(a), stream_ptr(x.device)), "gava_mix_clips")
+    return out
+
+
+def mix_targets(labels, desc, C_, smoothing=0.0):
+    """targets fp32 [B, C] = lam * s(label) + (1 - lam) * s(partner's label), s = the label smoothed by `smoothing`
+    (gava_mix_targets).  labels: device integer [B] (clamped to [0, C) on the device).  One launch, no sync."""
+    _on_device("mix_targets", labels)
+    _require(not labels.is_floating_point() and labels.dim() == 1 and labels.shape[0] == desc["B"],
+             "mix_targets takes integer class labels [B], one per descriptor")
+    _require(0.0 <= float(smoothing) <= 1.0 and int(C_) >= 1, "mix_targets: smoothing must lie in [0, 1] and C >= 1")
+    labels = labels.to(torch.int64).contiguous()
+    targets = torch.empty(desc["B"], int(C_), dtype=torch.float32, device=labels.device)
+    a = MixTargetsArgs()
+    a.labels, a.desc, a.targets, a.ld_targets = ptr(labels), ptr(desc["dev"]), ptr(targets), int(C_)
+    a.B, a.C, a.smoothing = desc["B"], int(C_), float(smoothing)
+    with torch.cuda.device(labels.device):
+        check(load().gava_mix_targets(C.byref(a), stream_ptr(labels.device)), "gava_mix_targets")
+    return targets
+
+
+def _row_stride(t):
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+
+
+def _soft_args(logits, targets, weighted, alpha, gamma, beta, scale):
+    _f32(logits, "logits"), _f32(targets, "targets")
+    assert logits.dim() == 2 and (logits.shape[1] == 1 or logits.stride(1) == 1), "logits must be [B, C] with a contiguous class dimension"
+    assert targets.shape == logits.shape and (targets.shape[1] == 1 or targets.stride(1) == 1) and targets.device == logits.device, \
+        "targets must be [B, C] like the logits, with a contiguous class dimension"
+    a = SoftCriterionArgs()
+    a.logits, a.ld_logits, a.targets, a.ld_targets = ptr(logits), _row_stride(logits), ptr(targets), _row_stride(targets)
+    a.B, a.C, a.weighted = logits.shape[0], logits.shape[1], int(weighted)
+    a.alpha, a.gamma, a.beta, a.scale = alpha, gamma, beta, scale
+    return a
+
+
+def soft_criterion(logits, targets, *, weighted=False, alpha=0.25, gamma=2.0, beta=0.0, scale=1.0, conf=None):
+    """The criterion for targets of the logits' shape (gava_soft_criterion; the formula is in include/gava_hip.h): per-sample
+    cross-entropy with class probabilities (times the ordinal-focal weight when `weighted`), its mean, both argmaxes and the
+    hit count.  logits, targets: device fp32 [B, C] with a contiguous class dimension (any row stride).  conf: optional device
+    int32 [C, C], ACCUMULATED: conf[target1, top1] += 1.
+    -> dict(loss (0-dim), per_sample [B], weight [B], top1 int32 [B], target1 int32 [B], hits int32 (0-dim), conf, saved [B, 8]).
+    Two launches, no sync."""
+    if not torch.is_tensor(targets) or not targets.is_floating_point() or targets.dim() != 2:
+        raise GavaError("gava_soft_criterion takes fp32 targets [B, C] of the logits' shape; integer class labels go to "
+                        "train_criterion (TrainCriterion)")
+    a = _soft_args(logits, targets, weighted, alpha, gamma, beta, scale)
+    B, Cn, dev = a.B, a.C, logits.device
+    out = dict(loss=torch.empty((), dtype=torch.float32, device=dev), per_sample=torch.empty(B, dtype=torch.float32, device=dev),
+               weight=torch.empty(B, dtype=torch.float32, device=dev), top1=torch.empty(B, dtype=torch.int32, device=dev),
+               target1=torch.empty(B, dtype=torch.int32, device=dev), hits=torch.empty((), dtype=torch.int32, device=dev), conf=conf,
+               saved=torch.empty(B, 8, dtype=torch.float32, device=dev))
+    if conf is not None:
+        assert conf.is_cuda and conf.dtype == torch.int32 and tuple(conf.shape) == (Cn, Cn) and conf.is_contiguous()
+    a.loss, a.per_sample, a.weight, a.top1, a.target1, a.hits = (ptr(out[k]) for k in ("loss", "per_sample", "weight", "top1", "target1", "hits"))
+    a.conf, a.saved = ptr(conf), ptr(out["saved"])
+    with torch.cuda.device(dev):
+        check(load().gava_soft_criterion(C.byref(a), stream_ptr(dev)), "gava_soft_criterion")
+    return out
+
+
+def soft_criterion_backward(logits, targets, saved, grad_loss, *, weighted=False, alpha=0.25, gamma=2.0, beta=0.0, scale=1.0):
+    """dlogits [B, C] of soft_criterion's loss (the same keywords as the forward); grad_loss: the upstream gradient, a DEVICE
+    fp32 scalar (never read on the host).  The targets receive no gradient."""
+    a = _soft_args(logits, targets, weighted, alpha, gamma, beta, scale)
+    _f32(grad_loss, "grad_loss")
+    assert grad_loss.numel() == 1 and tuple(saved.shape) == (a.B, 8) and saved.is_contiguous()
+    dlogits = torch.empty(a.B, a.C, dtype=torch.float32, device=logits.device)
+    a.saved, a.grad_loss, a.dlogits, a.ld_dlogits = ptr(saved), ptr(grad_loss), ptr(dlogits), a.C
+    with torch.cuda.device(logits.device):
+        check(load().gava_soft_criterion_backward(C.byref(a), stream_ptr(logits.device)), "gava_soft_criterion_backward")
     return dlogits
 
 

@@ -580,8 +580,8 @@ class VisionTowerFn(torch.autograd.Function):
 # With VitaCLIP.train_head = "hip" the head between the towers' outputs and the logits is HeadFn (the inference head's kernels
 # forward, fp32 MFMA tiles backward) instead of the traced torch ops of VitaCLIP._train_head, and TrainCriterion is the
 # criterion of training/train.py:360-362,446-452 (cross-entropy x ordinal-focal weight of training/loss_utils.py:9-46, mean)
-# as two launches forward and one backward.  Not covered: soft (mixup) labels and the InfoNCE variants of loss_utils.py - those
-# stay torch code on the caller's side; the auxiliary heads and their terms (the sigmoid memory criterion among them) are further down.
+# as two launches forward and one backward.  Not covered here: soft (mixup) labels - they have their own route below (ClipMixer,
+# SoftTargetCriterion) - and the InfoNCE variants of loss_utils.py, which stay torch code on the caller's side; the auxiliary heads and their terms (the sigmoid memory criterion among them) are further down.
 
 class HeadFn(torch.autograd.Function):
     """(logits [B, C], text_features [C, E]) = head(video [B, E], text [P, E], logit_scale, logit_bias or None, class_offsets):
@@ -658,6 +658,178 @@ class TrainCriterion:
         if self.track_confusion and (self.conf is None or self.conf.shape[0] != logits.shape[1] or self.conf.device != logits.device):
             self.conf = torch.zeros(logits.shape[1], logits.shape[1], dtype=torch.int32, device=logits.device)
         return _CriterionFn.apply(logits, labels.to(logits.device), self)
+
+
+# =================================================================================================
+# Mixup / CutMix on the device and the criterion for the soft targets they make (opt-in)
+# =================================================================================================
+# The reference's loss code takes targets of the logits' shape (training/loss_utils.py:32-44, CrossEntropyLoss with class
+# probabilities) and its loop keeps the branch for them (training/train.py:477), but it ships no mixing code.  ClipMixer mixes
+# a preprocessed fp32 batch and builds the targets (gava_mix_clips, gava_mix_targets); SoftTargetCriterion is the criterion for
+# them (gava_soft_criterion*), under autograd like TrainCriterion.  TrainCriterion and AuxCriterion keep their integer labels.
+# Not covered: a gradient through the mix to x, mixing uint8 frames (call pre.batch(videos), then the mixer), the memory batch.
+
+class _SoftCriterionFn(torch.autograd.Function):
+    @staticmethod
+    def forward(fctx, logits, targets, crit):
+        kw = dict(weighted=crit.focal_ordinal, alpha=crit.alpha, gamma=crit.gamma, beta=crit.beta, scale=crit.scale)
+        out = hip.soft_criterion(logits.detach(), targets, conf=crit.conf, **kw)
+        fctx.save_for_backward(logits.detach(), targets, out["saved"])
+        fctx.kw = kw
+        crit.last = {k: out[k] for k in ("per_sample", "weight", "top1", "target1", "hits", "conf")}
+        return out["loss"]
+
+    @staticmethod
+    def backward(fctx, g):
+        logits, targets, saved = fctx.saved_tensors
+        return hip.soft_criterion_backward(logits, targets, saved, g.float().contiguous(), **fctx.kw), None, None
+
+
+class SoftTargetCriterion:
+    """loss = crit(logits, targets): the reference's criterion for targets of the logits' shape, on the device
+    (gava_soft_criterion).  focal_ordinal=False is torch.nn.CrossEntropyLoss()(logits, targets) with class probabilities;
+    True multiplies every sample's cross-entropy by scale * (beta * |argmax targets - argmax logits| / (C - 1) * sum(targets)
+    + alpha * sum_c targets_c (1 - p_c)^gamma) before the mean (training/loss_utils.py:32-44 with a y_true of the logits'
+    shape).  Device fp32 [B, C] logits and device fp32 [B, C] targets (what ClipMixer returns); integer labels are refused -
+    they go to TrainCriterion.  No gradient flows to the targets.  After a call, `last` holds device tensors per_sample,
+    weight, top1, target1 (int32: the argmax of the logits and of the targets), hits (int32 scalar, #{top1 == target1}) and
+    conf; nothing is read back.  track_confusion=True keeps an int32 [C, C] matrix conf[target1, top1] that every call adds
+    to (reset_confusion() clears it)."""
+
+    def __init__(self, focal_ordinal=False, alpha=0.25, gamma=2.0, beta=0.0, scale=1.0, track_confusion=False):
+        if focal_ordinal and not gamma >= 1.0:
+            raise hip.GavaError("SoftTargetCriterion needs gamma >= 1: the focal factor's derivative is unbounded at p = 1 below that")
+        self.focal_ordinal, self.alpha, self.gamma, self.beta, self.scale = bool(focal_ordinal), float(alpha), float(gamma), float(beta), float(scale)
+        self.track_confusion = track_confusion
+        self.conf, self.last = None, {}
+
+    def reset_confusion(self):
+        self.conf = None
+
+    def __call__(self, logits, targets):
+        if not (torch.is_tensor(targets) and targets.is_floating_point() and targets.dim() == 2):
+            raise hip.GavaError("SoftTargetCriterion takes fp32 targets [B, C] of the logits' shape; integer class labels [B] go to TrainCriterion")
+        if not (logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2):
+            raise hip.GavaError("SoftTargetCriterion takes device fp32 logits [B, C]")
+        if not (targets.is_cuda and targets.dtype == torch.float32 and targets.shape == logits.shape and targets.device == logits.device):
+            raise hip.GavaError("SoftTargetCriterion takes device fp32 targets of the logits' shape, on the logits' device")
+        if logits.shape[1] > 1 and logits.stride(1) != 1:
+            logits = logits.contiguous()
+        targets = targets.detach()
+        if targets.shape[1] > 1 and targets.stride(1) != 1:
+            targets = targets.contiguous()
+        if self.track_confusion and (self.conf is None or self.conf.shape[0] != logits.shape[1] or self.conf.device != logits.device):
+            self.conf = torch.zeros(logits.shape[1], logits.shape[1], dtype=torch.int32, device=logits.device)
+        return _SoftCriterionFn.apply(logits, targets, self)
+
+
+class ClipMixer:
+    """x_mixed, targets = mixer(x, labels): Mixup / CutMix of a preprocessed batch on the device (gava_mix_clips) and the soft
+    targets that go with it (gava_mix_targets), for SoftTargetCriterion.  x: device fp32 [B, 3, T, S, S]; labels: device
+    integer [B]; -> x's shape, fp32 [B, C].  Clip i is mixed with clip B - 1 - i (the middle clip of an odd batch stays as it
+    is).  Mixup: lam x_i + (1 - lam) x_partner; CutMix: a box of the partner pasted through every frame.  mode: "batch" draws
+    once for the whole batch, "pair" once per pair, "elem" once per clip.  label_smoothing spreads eps over the classes before
+    the targets are mixed; ClipMixer(C, mixup_alpha=0, cutmix_alpha=0, label_smoothing=eps) is label smoothing alone.
+    inplace=True overwrites x.  No gradient flows through the mix.  Nothing is read back from the device."""
+
+    MODES = ("batch", "pair", "elem")
+
+    def __init__(self, num_classes, mixup_alpha=0.8, cutmix_alpha=1.0, prob=1.0, switch_prob=0.5, mode="batch", label_smoothing=0.1,
+                 correct_lam=True, seed=None):
+        import numpy as np
+        if mode not in self.MODES:
+            raise hip.GavaError(f"ClipMixer: mode must be one of {self.MODES}")
+        if not (int(num_classes) >= 1 and mixup_alpha >= 0 and cutmix_alpha >= 0 and 0 <= prob <= 1 and 0 <= switch_prob <= 1
+                and 0 <= label_smoothing <= 1):
+            raise hip.GavaError("ClipMixer: num_classes >= 1, alphas >= 0, prob, switch_prob and label_smoothing in [0, 1]")
+        self.num_classes, self.mixup_alpha, self.cutmix_alpha = int(num_classes), float(mixup_alpha), float(cutmix_alpha)
+        self.prob, self.switch_prob, self.mode = float(prob), float(switch_prob), mode
+        self.label_smoothing, self.correct_lam = float(label_smoothing), bool(correct_lam)
+        self.rng = np.random.default_rng(seed)
+        self.last_plan = None
+
+    def _draw_one(self, H, W):
+        """(lam, box) of one mixed-or-not unit."""
+        rng = self.rng
+        none = (1.0, (0, 0, 0, 0))
+        if not (self.mixup_alpha > 0 or self.cutmix_alpha > 0) or rng.random() >= self.prob:
+            return none
+        if self.mixup_alpha > 0 and self.cutmix_alpha > 0:
+            cut = rng.random() < self.switch_prob
+        else:
+            cut = self.cutmix_alpha > 0
+        if not cut:
+            return float(rng.beta(self.mixup_alpha, self.mixup_alpha)), (0, 0, 0, 0)
+        lam = float(rng.beta(self.cutmix_alpha, self.cutmix_alpha))
+        ratio = (1.0 - lam) ** 0.5
+        ch, cw = int(H * ratio), int(W * ratio)
+        cy, cx = int(rng.integers(0, H)), int(rng.integers(0, W))
+        y0, y1 = min(max(cy - ch // 2, 0), H), min(max(cy + ch // 2, 0), H)
+        x0, x1 = min(max(cx - cw // 2, 0), W), min(max(cx + cw // 2, 0), W)
+        if self.correct_lam:
+            lam = 1.0 - (y1 - y0) * (x1 - x0) / float(H * W)
+        if y1 <= y0 or x1 <= x0:                       # nothing is pasted: the clip keeps its pixels and its label
+            return none
+        return lam, (y0, y1, x0, x1)
+
+    def draw(self, B, H=224, W=None):
+        """The host plan of one batch: dict(partner int32 [B], lam float32 [B], box int32 [B, 4] as (y0, y1, x0, x1)), numpy.
+        partner[i] = B - 1 - i.  With probability `prob` a batch / pair / clip (by `mode`) is mixed: CutMix with probability
+        switch_prob when both alphas are positive (otherwise whichever is), lam ~ Beta(alpha, alpha) of the chosen kind.  The
+        CutMix box has its centre uniform in the image and sides H sqrt(1 - lam), W sqrt(1 - lam), clipped to the image; with
+        correct_lam, lam becomes 1 - area / (H W) of the clipped box.  Unmixed clips get lam = 1 and an empty box.  Everything
+        is drawn from the mixer's own numpy generator (np.random.default_rng(seed)) and from nothing else: the reference ships
+        no mixing code, so there is no generator order to stay in step with."""
+        import numpy as np
+        W = H if W is None else W
+        partner = (B - 1 - np.arange(B)).astype(np.int32)
+        lam, box = np.ones(B, dtype=np.float32), np.zeros((B, 4), dtype=np.int32)
+        if self.mode == "batch":
+            l, b = self._draw_one(H, W)
+            lam[:], box[:] = l, b
+        elif self.mode == "pair":
+            for i in range((B + 1) // 2):
+                l, b = self._draw_one(H, W)
+                lam[i] = lam[B - 1 - i] = l
+                box[i] = box[B - 1 - i] = b
+        else:
+            for i in range(B):
+                lam[i], box[i] = self._draw_one(H, W)
+        return dict(partner=partner, lam=lam, box=box)     # the middle clip of an odd batch is its own partner: untouched
+
+    @torch.no_grad()
+    def __call__(self, x, labels, plan=None, inplace=False):
+        import numpy as np
+        if not (torch.is_tensor(x) and torch.is_tensor(labels)):
+            raise hip.GavaError("ClipMixer takes tensors")
+        if not (x.is_cuda and labels.is_cuda):
+            raise hip.GavaError("ClipMixer takes device tensors: there is no CPU fallback")
+        if x.dtype != torch.float32 or x.dim() < 3:
+            raise hip.GavaError("ClipMixer takes fp32 clips [B, 3, T, S, S] (preprocessed; uint8 frames go through pre.batch first)")
+        if x.requires_grad:
+            raise hip.GavaError("ClipMixer: x requires grad, and no gradient flows through the mix")
+        if labels.is_floating_point() or labels.dim() != 1 or labels.shape[0] != x.shape[0]:
+            raise hip.GavaError("ClipMixer takes integer class labels [B]; it makes the soft targets itself")
+        if inplace and not x.is_contiguous():
+            raise hip.GavaError("ClipMixer: inplace=True needs a contiguous x")
+        B, H, W = x.shape[0], x.shape[-2], x.shape[-1]
+        if plan is None:
+            plan = self.draw(B, H, W)
+        self.last_plan = plan
+        desc = hip.mix_descriptors(plan, H, W, device=x.device)
+        lam, partner = np.asarray(plan["lam"]).reshape(-1), np.asarray(plan["partner"]).reshape(-1)
+        box = np.asarray(plan["box"]).reshape(-1, 4)
+        boxed = (box[:, 1] > box[:, 0]) & (box[:, 3] > box[:, 2])
+        if partner.shape[0] != B or lam.shape[0] != B or box.shape[0] != B:
+            raise hip.GavaError("ClipMixer: the plan is for another batch size")
+        mixed = (partner != np.arange(B)) & (boxed | (lam != 1))
+        if not mixed.any() and not (((partner >= 0) & (partner < B)).all() and ((lam >= 0) & (lam <= 1)).all()):
+            raise hip.GavaError("ClipMixer: the plan's partners must lie in [0, B) and its lam in [0, 1]")      # no launch validates it
+        if mixed.any():
+            xc = x if x.is_contiguous() else x.contiguous()
+            x = hip.mix_clips(xc, desc, out=xc if inplace else None)
+        targets = hip.mix_targets(labels.to(x.device), desc, self.num_classes, self.label_smoothing)
+        return x, targets
 
 
 # =================================================================================================

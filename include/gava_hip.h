@@ -1103,6 +1103,92 @@ int gava_path_delta(const gava_path_delta_args* a, gava_stream_t stream);
  * gava_perturbation_struct_sizes.  Writes min(cap, 4) entries, returns 4. */
 int gava_path_grad_struct_sizes(size_t* out, int cap);
 
+/* ---- Mixup / CutMix on the device and the criterion for soft targets (opt-in: gava_clip_amd.ClipMixer, SoftTargetCriterion) --
+ *
+ * The reference's loss code takes targets of the logits' shape (training/loss_utils.py:32-44 and CrossEntropyLoss with class
+ * probabilities); its loop keeps the branch for them (training/train.py:477) but ships no mixing code.  This section is the
+ * mix of the clips, the targets that go with it, and that criterion.  gava_train_criterion and the sigmoid criterion keep
+ * taking integer labels only.  fp32 throughout, no floating-point atomics: the same bits on every run.
+ *
+ * gava_mix_clips: x, out fp32 [B][planes][H][W], contiguous (planes = 3 T for a [B, 3, T, S, S] batch), one descriptor per
+ * clip.  For clip i with partner j = desc[i].partner, own pixel a and the partner's pixel b at the same position:
+ *   j == i                         out = a: a copy, bit for bit (nothing is computed)
+ *   y1 > y0 && x1 > x0  (CutMix)   out = b where y0 <= h < y1 and x0 <= w < x1 (a tube through all planes), a elsewhere: a
+ *                                  selection, bit for bit; lam is not read
+ *   otherwise           (Mixup)    out = fma(lam, a, fl(fl(1 - lam) * b)); lam == 1 copies a and lam == 0 copies b, whatever
+ *                                  the values
+ * out != x: any partner; x and out must not overlap.  out == x (in place): partner must be an involution
+ * (partner[partner[i]] == i); one thread owns a position of both clips of a pair, reads both originals and writes both
+ * results, each by its clip's own descriptor, so the members of a pair may differ in lam, box and kind - with the bits of
+ * the out-of-place call.  Positions that no descriptor changes are not written in place.  Rows are walked with 16-byte
+ * accesses when W % 4 == 0 and both bases are 16-byte aligned (box edges off a multiple of 4 select per element inside the
+ * vector), element by element otherwise; no address outside the tensors is formed.  The grid's y extent is the clip, split
+ * into launches of 65535 clips; within a clip a grid-stride loop.
+ * The arguments carry the descriptor table twice: desc_host is read by the entry point, desc (the same B entries in device
+ * memory) by the kernel.  GAVA_EINVAL, before any launch: a null pointer; B, planes, H or W < 1; planes * H * W >= 2^31; a
+ * partner outside [0, B); a box outside [0, H] x [0, W] or inverted (y1 < y0 or x1 < x0); lam outside [0, 1] or NaN;
+ * out == x with a partner table that is no involution; x and out overlapping without being equal.
+ *
+ * gava_mix_targets: targets [B][C] fp32 (rows ld_targets apart) from int64 labels (DEVICE, clamped to [0, C) like
+ * gava_train_criterion's), the same device descriptor table and a label smoothing eps in [0, 1]:
+ *   s(y)[c] = (1 - eps) [c == y] + eps / C;   targets[i] = lam_i s(y_i) + (1 - lam_i) s(y_partner(i))
+ * formed in fp64 and rounded once; exact for eps == 0 and lam in {0, 1}; a clip that is its own partner gets s(y_i) whatever
+ * its lam.  One launch.  The descriptors are not validated
+ * here (they are device memory); a partner outside [0, B) is clamped.
+ *
+ * gava_soft_criterion / gava_soft_criterion_backward: per sample i with logits z, targets t >= 0 of the same shape and
+ * tau = sum_c t_c (need not be 1):
+ *   p = softmax(z);  lse = logsumexp(z);  ce = sum_c t_c (lse - z_c)                 (every term >= 0)
+ *   k = argmax_c z_c,  y* = argmax_c t_c                                             (the lowest index on ties, as torch.argmax)
+ *   w = scale * (fl32(beta * fl32(|y* - k| / (C - 1))) * tau + alpha * sum_c t_c (1 - p_c)^gamma)
+ *   l = weighted ? ce * w : ce;   loss = mean_i l_i;   hits = #{i : k_i == y*_i};   conf[y*][k] += 1 (optional, ACCUMULATED)
+ *   Q = sum_c t_c (1 - p_c)^(gamma - 1) p_c
+ *   dlogits[i][c] = (w (tau p_c - t_c) + ce scale alpha gamma p_c (Q - t_c (1 - p_c)^(gamma - 1))) * grad_loss / B
+ * (unweighted: (tau p_c - t_c) * grad_loss / B; the ordinal term has no gradient, as in the reference).  With one-hot targets
+ * this is gava_train_criterion's formula.  One wave per sample: logsumexp = m + log1p(s1) with m the row maximum and s1 the
+ * sum of exp(z_c - m) over the other classes; 1 - p_c = s1 / (1 + s1) for the top class, ((1 + s1) - e_c) / (1 + s1)
+ * otherwise.  Classes with t_c == 0 add nothing: an all-zero target row has loss and gradient exactly 0.  The forward leaves
+ * eight floats per sample in `saved` (m, log1p(s1), s1, the bits of k; w, ce scale alpha gamma, Q, tau); the backward reads
+ * them, the logits, the targets, `weighted` and `gamma` from the same struct, and the upstream gradient FROM DEVICE MEMORY
+ * (grad_loss, one float).  No gradient is formed for the targets.
+ * GAVA_EINVAL: weighted with gamma < 1 or C < 2, B < 1, C < 1, a row stride below C, a null pointer among the required ones
+ * (forward: logits, targets, loss, per_sample, weight, top1, target1, hits, saved; backward: logits, targets, saved,
+ * grad_loss, dlogits).  Two launches forward, one backward, no host synchronisation. */
+typedef struct { int32_t partner; float lam; int32_t y0, y1, x0, x1; } gava_mix_desc;
+
+typedef struct {
+  const float* x; float* out;                 /* fp32 [B][planes][H][W]; out == x mixes in place */
+  const gava_mix_desc* desc_host;             /* [B], host memory: validated by the entry point */
+  const gava_mix_desc* desc;                  /* [B], the same table in device memory: read by the kernel */
+  int B, planes, H, W;
+} gava_mix_clips_args;
+int gava_mix_clips(const gava_mix_clips_args* a, gava_stream_t stream);
+
+typedef struct {
+  const int64_t* labels;                      /* DEVICE [B] */
+  const gava_mix_desc* desc;                  /* DEVICE [B] */
+  float* targets; int64_t ld_targets;         /* fp32 [B][C] */
+  int B, C; float smoothing; int reserved;
+} gava_mix_targets_args;
+int gava_mix_targets(const gava_mix_targets_args* a, gava_stream_t stream);
+
+typedef struct {
+  const float* logits; int64_t ld_logits;     /* fp32 [B][C], rows ld_logits elements apart */
+  const float* targets; int64_t ld_targets;   /* fp32 [B][C], rows ld_targets elements apart */
+  int B, C, weighted;
+  float alpha, gamma, beta, scale;
+  float* loss; float* per_sample; float* weight; int32_t* top1; int32_t* target1; int32_t* hits;
+  int32_t* conf;                              /* optional */
+  float* saved;                               /* [B][8] */
+  const float* grad_loss; float* dlogits; int64_t ld_dlogits;     /* backward only */
+} gava_soft_criterion_args;
+int gava_soft_criterion(const gava_soft_criterion_args* a, gava_stream_t stream);
+int gava_soft_criterion_backward(const gava_soft_criterion_args* a, gava_stream_t stream);
+
+/* sizeof of gava_mix_desc, gava_mix_clips_args, gava_mix_targets_args, gava_soft_criterion_args, in that order, like
+ * gava_path_grad_struct_sizes.  Writes min(cap, 4) entries, returns 4. */
+int gava_mix_struct_sizes(size_t* out, int cap);
+
 /* sizeof of every ABI struct as the library was compiled, in the order gemm_args, layernorm_args, attention_args,
  * attention_f32_args, clip_desc, vision_layer, vision_layer8, vision_model, text_layer, text_model, layernorm_bwd_args,
  * attention_bwd_args, vision_saved, preprocess_args, patchify_args, preprocess_clips_args, view_scores_args.  Writes
