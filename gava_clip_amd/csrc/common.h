@@ -75,8 +75,10 @@ static __device__ __forceinline__ void split4(float a, float b, float c, float d
                 c - P::up((unsigned short)hi.y), d - P::up((unsigned short)(hi.y >> 16)));
 }
 
-// the residual stream's pair: hi in the operand type, lo = fp16 of the remainder whatever the operand type (2^-22 of |x| with
-// fp16 operands, 2^-20 with bf16 ones)
+// the residual stream's pair: hi in the operand type, lo = fp16 of the remainder whatever the operand type.  x - hi is exact in
+// fp32 and at most eps16 |x| (eps16 = 2^-11 fp16, 2^-8 bf16: half a unit in the last place); its fp16 rounding loses 2^-11 of
+// that, 2^-25 absolute below the fp16 normal range: |x - hi - lo| <= max(2^-22 |x|, 2^-25) with fp16 operands, 2^-19 |x| with
+// bf16 ones (tests/rowops_ref.py pair_bound)
 template <class P>
 static __device__ __forceinline__ void split4_lo16(float a, float b, float c, float d, uint2& hi, uint2& lo) {
   hi.x = P::cvt2(a, b);

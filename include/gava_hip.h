@@ -194,7 +194,7 @@ typedef struct {
    * the operand type) and the result x = resid + A W^T + bias leaves as x16_out = h16(x) and xlo_out = fp16(x - h16(x)) (both
    * [M][ld_x16]) together with the producer's row sums (rowsum_out, computed from the fp32 x): 8 bytes per element through the
    * epilogue instead of 10 (fp32 in, fp32 out, 16-bit copy), and the hi half IS the operand of the GEMM that consumes the
-   * LayerNorm fold.  |x - hi - lo| <= 2^-22 |x| (fp16 operands; 2^-20 with bf16).  out and resid must be NULL, x16_out /
+   * LayerNorm fold.  |x - hi - lo| <= 2^-22 |x| (fp16 operands; 2^-19 with bf16).  out and resid must be NULL, x16_out /
    * xlo_out may alias resid16 / resid_lo (every element is read and written by the same lane).  The persistent 256 x 256
    * kernel with the ping-pong loop only (N % 256 == 0, K % 128 == 0, K >= 256, w_lo <= 1); rejected elsewhere. */
   const void* resid16; const void* resid_lo; void* xlo_out;
@@ -471,7 +471,9 @@ int gava_text_forward_train(const gava_text_model* m, const int32_t* tokens, con
                             size_t workspace_bytes, gava_stream_t stream);
 
 /* (mean, rstd) per row from the producers' partial sums: rowsum float2 [rows][slots] -> stats float2 [rows], D columns,
- * eps 1e-5, variance = E[x^2] - mean^2 in fp32 with a fixed summation order (deterministic). */
+ * eps 1e-5, variance = max(E[x^2] - mean^2, 0) in fp32 with a fixed summation order (deterministic).  The difference cancels:
+ * its error is 2^-24 (E[x^2] + mean^2) times a small constant, whatever the variance - rows on a large common offset lose
+ * that much of rstd (profiles/rowops_edges_errors.txt, row_stats / offset).  1 <= slots <= 32. */
 int gava_row_stats(const float* rowsum, int slots, int D, int rows, float* stats, gava_stream_t stream);
 
 /* gava_vision_forward that also keeps what the backward recomputes from: saved_x fp32 [layers+2][B*T_in*(n+1)][D] =
@@ -553,7 +555,9 @@ typedef struct {
 } gava_patchify_args;
 int gava_patchify(const gava_patchify_args* a, gava_stream_t stream);
 
-/* fp32 -> h16 conversion of a contiguous array (weight packing at load time). */
+/* fp32 -> h16 conversion of a contiguous array (weight packing at load time).  Round to nearest even, ties included; results
+ * below the 16-bit normal range are subnormals (nothing is flushed), fp16 overflows to inf from 65520 on, NaN stays NaN.
+ * n = 0 is accepted and writes nothing. */
 int gava_convert_h16(const float* in, void* out, size_t n, int prec, gava_stream_t stream);
 
 /* ---- training head and criterion (opt-in: VitaCLIP.train_head = "hip", gava_clip_amd.TrainCriterion) ----------------------
