@@ -402,3 +402,31 @@ def test_refused_outside_evaluation_and_leaves_no_trace():
         m.cache_text_features = before
     for n, p in m.named_parameters():
         assert (p.grad is None) == (grads[n] is None) and (p.grad is None or torch.equal(p.grad, grads[n])), n
+
+
+def test_blurred_curves_add_no_host_synchronisation():
+    """Counted as tests/test_gpu_path_grad.py counts the path calls': the blur baseline's taps go up from pinned memory, so
+    the call - three clips in an uneven 2 + 1 split, top-1 or a given target - waits for the device no more often than the
+    plain no-grad forward of the same clips."""
+    import warnings
+    m, x = model("fp16"), clip(3)
+    s = patch_scores(3, x.shape[2]).cuda()
+    S1 = 4
+
+    def count(fn):
+        with torch.no_grad():
+            fn()                                    # warm-up: packs, workspaces, the side stream
+            torch.cuda.synchronize()
+            torch.cuda.set_sync_debug_mode("warn")
+            try:
+                with warnings.catch_warnings(record=True) as caught:
+                    warnings.simplefilter("always")
+                    fn()
+            finally:
+                torch.cuda.set_sync_debug_mode("default")
+        return len([w for w in caught if "synchroniz" in str(w.message).lower()])
+
+    curves = lambda **kw: m.perturbation_curves(x, s, steps=S1 - 1, baseline="blur", max_clips=2 * S1, **kw)
+    n_plain, n_top1, n_target = count(lambda: m(x)), count(curves), count(lambda: curves(target=1))
+    print(f"\n[perturbation] host synchronisations: forward {n_plain}, blurred curves (top-1) {n_top1}, (target) {n_target}")
+    assert n_top1 <= n_plain and n_target <= n_plain
