@@ -22,6 +22,9 @@ def __getattr__(name):  # lazy: importing the package must not need torch/HIP
     if name in ("ClipMixer", "SoftTargetCriterion"):
         from . import training
         return getattr(training, name)
+    if name in ("RandAugment", "AugmentedClipPreprocessor"):
+        from . import augment
+        return getattr(augment, name)
     if name == "AuxCriterion":
         from .training import AuxCriterion
         return AuxCriterion

@@ -18,7 +18,7 @@ LIB = os.path.join(HERE, "libgava_hip.so")
 HASHFILE = LIB + ".srchash"
 SOURCES = ["gemm.hip", "attention.hip", "rowops.hip", "forward.hip", "preprocess.hip", "backward.hip", "attention_bwd.hip", "train_head.hip",
            "aux_heads.hip", "optimizer.hip", "input_grad.hip", "attention_maps.hip",
-           "attention_relevance.hip", "perturbation.hip", "path_grad.hip", "mix.hip"]
+           "attention_relevance.hip", "perturbation.hip", "path_grad.hip", "mix.hip", "augment.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 
 

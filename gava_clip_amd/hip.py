@@ -39,7 +39,11 @@ EXPORTS = ["gava_abi_version", "gava_gemm", "gava_layernorm", "gava_attention",
            "gava_attention_relevance", "gava_attention_relevance_struct_sizes",
            "gava_patch_ranks", "gava_blur_clips", "gava_perturb_clips", "gava_perturb_scores", "gava_perturbation_struct_sizes",
            "gava_path_clips", "gava_clip_range", "gava_unpatchify_path", "gava_path_delta", "gava_path_grad_struct_sizes",
-           "gava_mix_clips", "gava_mix_targets", "gava_soft_criterion", "gava_soft_criterion_backward", "gava_mix_struct_sizes"]
+           "gava_mix_clips", "gava_mix_targets", "gava_soft_criterion", "gava_soft_criterion_backward", "gava_mix_struct_sizes",
+           "gava_augment_hist", "gava_augment_luts", "gava_augment_apply", "gava_augment_struct_sizes"]
+AUG_TABLE, AUG_COLOR, AUG_SHARPNESS, AUG_AFFINE = 0, 1, 2, 3      # gava_augment_desc.kind
+AUG_INVERT, AUG_POSTERIZE, AUG_SOLARIZE, AUG_SOLARIZE_ADD, AUG_BRIGHTNESS, AUG_CONTRAST, AUG_AUTOCONTRAST, AUG_EQUALIZE = range(8)      # .op
+AUG_BILINEAR, AUG_BICUBIC = 0, 1                                  # .filter
 ATTENTION_MASS_MAX_KEYS = 640     # gava_attention_mass keeps K of one (frame, head) resident in LDS
 ATTENTION_RELEVANCE_MAX_KEYS = 640     # and so does gava_attention_relevance
 PERTURB_MAX_UNITS = 65536         # patches or frames one gava_patch_ranks ranking holds
@@ -333,6 +337,17 @@ class SoftCriterionArgs(C.Structure):
                 ("saved", _fp), ("grad_loss", _fp), ("dlogits", _fp), ("ld_dlogits", C.c_int64)]
 
 
+class AugmentDesc(C.Structure):
+    _fields_ = [("src", _vp), ("dst", _vp), ("H", C.c_int32), ("W", C.c_int32), ("kind", C.c_int32), ("op", C.c_int32),
+                ("filter", C.c_int32), ("iarg", C.c_int32), ("factor", C.c_float), ("lut_slot", C.c_int32),
+                ("hist_slot", C.c_int32), ("reserved", C.c_int32), ("m", C.c_double * 6)]
+
+
+class AugmentArgs(C.Structure):
+    _fields_ = [("desc_host", C.c_void_p), ("desc", _vp), ("hist", _vp), ("luts", _vp),
+                ("n", C.c_int32), ("n_hist", C.c_int32), ("n_luts", C.c_int32), ("reserved", C.c_int32)]
+
+
 class VisionSaved(C.Structure):
     _fields_ = [("e0", _fp), ("x", _fp), ("x1", _fp), ("qkv", _vp), ("pre", _vp), ("sidekv", _vp),
                 ("last_q", _vp), ("last_x1", _fp), ("last_pre", _vp)]
@@ -560,6 +575,17 @@ def load():
     if lib.gava_mix_struct_sizes(sizes, len(mix_mirrors)) != len(mix_mirrors):
         raise GavaError("libgava_hip.so and gava_clip_amd/hip.py disagree on the number of mix ABI structs")
     for cls, sz in zip(mix_mirrors, sizes):
+        if C.sizeof(cls) != sz:
+            raise GavaError(f"ctypes mirror {cls.__name__} is {C.sizeof(cls)} bytes, the library's struct {sz}: gava_clip_amd/hip.py is out of "
+                            f"step with include/gava_hip.h")
+    # the augmentation's structs, the same way
+    augment_mirrors = [AugmentDesc, AugmentArgs]
+    for name in ("gava_augment_hist", "gava_augment_luts", "gava_augment_apply"):
+        getattr(lib, name).argtypes, getattr(lib, name).restype = [C.POINTER(AugmentArgs), _vp], C.c_int
+    lib.gava_augment_struct_sizes.argtypes, lib.gava_augment_struct_sizes.restype = [C.POINTER(C.c_size_t), C.c_int], C.c_int
+    if lib.gava_augment_struct_sizes(sizes, len(augment_mirrors)) != len(augment_mirrors):
+        raise GavaError("libgava_hip.so and gava_clip_amd/hip.py disagree on the number of augmentation ABI structs")
+    for cls, sz in zip(augment_mirrors, sizes):
         if C.sizeof(cls) != sz:
             raise GavaError(f"ctypes mirror {cls.__name__} is {C.sizeof(cls)} bytes, the library's struct {sz}: gava_clip_amd/hip.py is out of "
                             f"step with include/gava_hip.h")
@@ -1464,6 +1490,43 @@ def mix_targets(labels, desc, C_, smoothing=0.0):
     with torch.cuda.device(labels.device):
         check(load().gava_mix_targets(C.byref(a), stream_ptr(labels.device)), "gava_mix_targets")
     return targets
+
+
+# ---- RandAugment layers (gava_augment_*) ------------------------------------------------------------------------------------------
+
+def augment_desc_dtype():
+    """numpy's view of gava_augment_desc (a structured dtype with the struct's offsets)"""
+    import numpy as np
+    return np.dtype(AugmentDesc)
+
+
+def augment_layer(rows, hist, luts, device, stages=("hist", "luts", "apply")):
+    """One layer of an augmentation policy: `rows` is a numpy array of gava_augment_desc (augment_desc_dtype), one per frame;
+    hist / luts the device buffers its slots index (int32 [n_hist, 4, 256], zero before the first layer; uint8 [n_luts, 3, 256];
+    None where no row needs them).  The table goes to the device from pinned memory, non-blocking, and the three entry points
+    run in order (`stages`: a subset, for measurements).  The library validates the host table before every launch.  Nothing
+    waits.  -> (pinned host table, device table): keep them until the layer's successor is enqueued."""
+    import numpy as np
+    rows = np.ascontiguousarray(rows, dtype=augment_desc_dtype())
+    _require(rows.ndim == 1 and rows.shape[0] >= 1, "augment_layer: rows must hold at least one gava_augment_desc")
+    host = torch.empty(rows.nbytes, dtype=torch.uint8).pin_memory()
+    host.numpy()[:] = rows.view(np.uint8)
+    dev = host.to(device, non_blocking=True)
+    a = AugmentArgs()
+    a.desc_host, a.desc, a.n = host.data_ptr(), ptr(dev), rows.shape[0]
+    if hist is not None:
+        _require(hist.is_cuda and hist.dtype == torch.int32 and hist.is_contiguous() and hist.shape[1:] == (4, 256),
+                 "augment_layer: hist must be a contiguous device int32 tensor [n, 4, 256]")
+        a.hist, a.n_hist = ptr(hist), hist.shape[0]
+    if luts is not None:
+        _require(luts.is_cuda and luts.dtype == torch.uint8 and luts.is_contiguous() and luts.shape[1:] == (3, 256),
+                 "augment_layer: luts must be a contiguous device uint8 tensor [n, 3, 256]")
+        a.luts, a.n_luts = ptr(luts), luts.shape[0]
+    lib = load()
+    with torch.cuda.device(device):
+        for stage in stages:
+            check(getattr(lib, "gava_augment_" + stage)(C.byref(a), stream_ptr(device)), "gava_augment_" + stage)
+    return host, dev
 
 
 def _row_stride(t):

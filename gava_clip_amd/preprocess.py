@@ -11,7 +11,8 @@ TrainClipPreprocessor is the `random_sample=True` branch of the upstream Vita-CL
 random temporal sampling (TSN included) and random_resized_crop (transform.py:503-577).  The random draws are index
 arithmetic on the host; normalisation and the bilinear resize of the drawn box run in the same kernels.
 
-Decoding (PyAV) and auto-augment (PIL, dataset.py:98-108) stay on the host.
+Decoding (PyAV) stays on the host.  The recipe's auto-augment step (dataset.py:98-108, Pillow upstream) is
+gava_clip_amd.augment.AugmentedClipPreprocessor, a TrainClipPreprocessor with RandAugment on the device in front.
 """
 import math
 import random
@@ -147,8 +148,9 @@ class TrainClipPreprocessor:
     def __init__(self, num_frames=8, sampling_rate=1, spatial_size=224, mean=CLIP_MEAN, std=CLIP_STD, auto_augment=None,
                  interpolation="bicubic", mirror=False):
         if auto_augment is not None:
-            raise NotImplementedError("auto_augment is PIL work on the host (dataset.py:98-108): augment there, then use "
-                                      "auto_augment=None here")
+            raise NotImplementedError("auto_augment (dataset.py:98-108) is the work of gava_clip_amd.AugmentedClipPreprocessor("
+                                      f"{auto_augment!r}, ...), which runs RandAugment on the device; this class is the data path "
+                                      "without it")
         self.num_frames, self.sampling_rate, self.spatial_size = num_frames, sampling_rate, spatial_size
         self.mean = tuple(float(v) for v in torch.as_tensor(mean).flatten().tolist())
         self.std = tuple(float(v) for v in torch.as_tensor(std).flatten().tolist())

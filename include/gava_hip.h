@@ -1193,6 +1193,76 @@ int gava_soft_criterion_backward(const gava_soft_criterion_args* a, gava_stream_
  * gava_path_grad_struct_sizes.  Writes min(cap, 4) entries, returns 4. */
 int gava_mix_struct_sizes(size_t* out, int cap);
 
+/* ---- RandAugment on the device (opt-in: gava_clip_amd.RandAugment, AugmentedClipPreprocessor) ------------------------------------
+ *
+ * The reference's auto_augment step (video_dataset/dataset.py:98-108, rand_augment.py) runs its ops through Pillow on the host,
+ * between the frame draw and random_resized_crop.  This section is that step on packed uint8 RGB frames [H][W][3] (rows of 3 W
+ * bytes, no alignment asked), with Pillow's results byte for byte.  One call handles one LAYER of the policy: a table of n
+ * descriptors, one per frame, of any mix of sizes and ops; the host draws the policy and builds the tables.  Each entry point
+ * is one launch whatever n is (none where no frame of the layer needs it), nothing waits for the device, integer atomics only.
+ *
+ * kind GAVA_AUG_TABLE: dst[p][c] = lut[c][src[p][c]], the 3 x 256 table built by gava_augment_luts in slot lut_slot from op:
+ *   INVERT        255 - i                      POSTERIZE   i & ~(2^(8 - iarg) - 1)   (iarg >= 8: i)
+ *   SOLARIZE      i < iarg ? i : 255 - i       SOLARIZE_ADD  i < 128 ? min(255, i + iarg) : i
+ *   BRIGHTNESS    blend(0, i, factor)
+ *   CONTRAST      blend(mean, i, factor), mean = int(sum_i i hL[i] / sum_i hL[i] + 0.5) in fp64 from the histogram hL of
+ *                 L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16
+ *   AUTOCONTRAST  per channel, lo / hi the first / last non-empty bin: i if hi <= lo, else with scale = 255.0 / (hi - lo) in
+ *                 fp64 clamp(int(i * scale + (-lo * scale)), 0, 255), int truncating toward zero
+ *   EQUALIZE      per channel, in integers: with the non-empty bins nz, step = (sum nz - nz[last]) / 255; i if there is at most
+ *                 one non-empty bin or step == 0, else min(255, (step / 2 + sum_{j < i} h[j]) / step)
+ *   The last three read the frame's histograms - uint32 [4][256] for R, G, B, L in slot hist_slot - which gava_augment_hist
+ *   counts from src (CONTRAST: L only; the other two: R, G, B only).  The histogram buffer must be zero before the first layer;
+ *   gava_augment_luts zeroes every slot it reads, so the buffer is ready for the next layer.
+ * kind GAVA_AUG_COLOR: dst = blend(L, v, factor) per channel.
+ * kind GAVA_AUG_SHARPNESS: dst = blend(smooth(v), v, factor); smooth is Pillow's SMOOTH filter: fp32, from 0.5, adding
+ *   pixel * fl32(k / 13) row-major with k = 1 1 1 / 1 5 1 / 1 1 1, clipped to [0, 255] and truncated; the one-pixel border is
+ *   copied.
+ * kind GAVA_AUG_AFFINE: Image.transform(AFFINE, m, filter, fill 128) in fp64: xin = m0 (xo + .5) + m1 (yo + .5) + m2, yin
+ *   likewise from m3..m5; outside [0, W) x [0, H) the pixel is 128; else xin -= .5, x = floor(xin), dx = xin - x (and y), and
+ *   BILINEAR  v = a + (b - a) d along x on rows clip(y), clip(y + 1), then along y; truncated
+ *   BICUBIC   rows clip(y - 1 .. y + 2), columns clip(x - 1 .. x + 2); p1 = v2, p2 = -v1 + v3, p3 = 2 (v1 - v2) + v3 - v4,
+ *             p4 = -v1 + v2 - v3 + v4, v = p1 + d (p2 + d (p3 + d p4)) along x, then along y; <= 0 -> 0, >= 255 -> 255, else
+ *             truncated
+ * blend(a, b, f) = a + fl32(f) (b - a) in fp32: truncated for 0 <= f <= 1, else clipped to [0, 255] and truncated.  No product
+ * is fused into the add that follows it (Pillow's CPU builds do not contract).
+ *
+ * The arguments carry the table twice, like gava_mix_clips: desc_host is validated by every entry point, desc (the same n
+ * entries in device memory) is read by the kernels.  GAVA_EINVAL, before any launch: a null table, n < 1, n_hist or n_luts < 0;
+ * per descriptor a null src or dst, H or W < 1, a frame of 2^31 bytes or more, src == dst (or overlapping frames), an unknown
+ * kind, op or filter, a non-finite factor or matrix entry, iarg outside [0, 256] for the ops that read it, a table op with
+ * luts null or lut_slot outside [0, n_luts), a statistics op with hist null or hist_slot outside [0, n_hist).  Fields a kind
+ * does not read are ignored apart from the finiteness of factor and m. */
+enum { GAVA_AUG_TABLE = 0, GAVA_AUG_COLOR = 1, GAVA_AUG_SHARPNESS = 2, GAVA_AUG_AFFINE = 3 };                 /* kind */
+enum { GAVA_AUG_INVERT = 0, GAVA_AUG_POSTERIZE = 1, GAVA_AUG_SOLARIZE = 2, GAVA_AUG_SOLARIZE_ADD = 3,         /* op of a table */
+       GAVA_AUG_BRIGHTNESS = 4, GAVA_AUG_CONTRAST = 5, GAVA_AUG_AUTOCONTRAST = 6, GAVA_AUG_EQUALIZE = 7 };
+enum { GAVA_AUG_BILINEAR = 0, GAVA_AUG_BICUBIC = 1 };                                                          /* filter */
+
+typedef struct {
+  const uint8_t* src; uint8_t* dst;           /* one frame each, uint8 [H][W][3] */
+  int32_t H, W, kind, op;
+  int32_t filter, iarg; float factor; int32_t lut_slot;
+  int32_t hist_slot, reserved;
+  double m[6];                                /* GAVA_AUG_AFFINE: output pixel centre -> source position */
+} gava_augment_desc;
+
+typedef struct {
+  const gava_augment_desc* desc_host;         /* [n], host memory: validated by the entry points */
+  const gava_augment_desc* desc;              /* [n], the same table in device memory: read by the kernels */
+  uint32_t* hist;                             /* DEVICE [n_hist][4][256], zero on entry to the first layer */
+  uint8_t* luts;                              /* DEVICE [n_luts][3][256] */
+  int32_t n, n_hist, n_luts, reserved;
+} gava_augment_args;
+/* a layer is these three calls in this order on one stream; the first two launch nothing where the layer needs no statistics /
+ * no table */
+int gava_augment_hist(const gava_augment_args* a, gava_stream_t stream);
+int gava_augment_luts(const gava_augment_args* a, gava_stream_t stream);
+int gava_augment_apply(const gava_augment_args* a, gava_stream_t stream);
+
+/* sizeof of gava_augment_desc, gava_augment_args, in that order, like gava_mix_struct_sizes.  Writes min(cap, 2) entries,
+ * returns 2. */
+int gava_augment_struct_sizes(size_t* out, int cap);
+
 /* sizeof of every ABI struct as the library was compiled, in the order gemm_args, layernorm_args, attention_args,
  * attention_f32_args, clip_desc, vision_layer, vision_layer8, vision_model, text_layer, text_model, layernorm_bwd_args,
  * attention_bwd_args, vision_saved, preprocess_args, patchify_args, preprocess_clips_args, view_scores_args.  Writes
