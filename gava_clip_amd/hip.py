@@ -34,6 +34,7 @@ EXPORTS = ["gava_abi_version", "gava_gemm", "gava_layernorm", "gava_attention",
            "gava_sigmoid_criterion", "gava_sigmoid_criterion_backward", "gava_nte_diag_loss", "gava_nte_diag_loss_backward",
            "gava_aux_struct_sizes",
            "gava_adamw_plan", "gava_adamw_step", "gava_optim_struct_sizes",
+           "gava_grad_norm", "gava_adamw_step_clipped", "gava_grad_clip_struct_sizes",
            "gava_unpatchify", "gava_input_grad_struct_sizes",
            "gava_attention_mass", "gava_attention_maps_struct_sizes",
            "gava_attention_relevance", "gava_attention_relevance_struct_sizes",
@@ -235,6 +236,12 @@ class AdamWArgs(C.Structure):
     _fields_ = [("table", _vp), ("table_host", C.POINTER(AdamWTensor)), ("chunks", _vp),
                 ("n_tensors", C.c_int), ("n_chunks", C.c_int), ("n_groups", C.c_int), ("reserved", C.c_int),
                 ("groups", AdamWGroup * 8), ("grad_scale", _fp), ("found_inf", _fp)]
+
+
+class GradNormArgs(C.Structure):
+    _fields_ = [("table", _vp), ("table_host", C.POINTER(AdamWTensor)), ("chunks", _vp),
+                ("n_tensors", C.c_int), ("n_chunks", C.c_int), ("n_groups", C.c_int), ("reserved", C.c_int),
+                ("grad_scale", _fp), ("max_norm", C.c_double), ("workspace", _vp), ("tensor_norm", _fp), ("stats", _fp)]
 
 
 class PatchifyArgs(C.Structure):
@@ -509,6 +516,17 @@ def load():
     if lib.gava_optim_struct_sizes(sizes, len(optim_mirrors)) != len(optim_mirrors):
         raise GavaError("libgava_hip.so and gava_clip_amd/hip.py disagree on the number of optimizer ABI structs")
     for cls, sz in zip(optim_mirrors, sizes):
+        if C.sizeof(cls) != sz:
+            raise GavaError(f"ctypes mirror {cls.__name__} is {C.sizeof(cls)} bytes, the library's struct {sz}: gava_clip_amd/hip.py is out of "
+                            f"step with include/gava_hip.h")
+    # the gradient clip's struct, the same way
+    grad_clip_mirrors = [GradNormArgs]
+    lib.gava_grad_norm.argtypes, lib.gava_grad_norm.restype = [C.POINTER(GradNormArgs), _vp], C.c_int
+    lib.gava_adamw_step_clipped.argtypes, lib.gava_adamw_step_clipped.restype = [C.POINTER(AdamWArgs), _fp, _vp], C.c_int
+    lib.gava_grad_clip_struct_sizes.argtypes, lib.gava_grad_clip_struct_sizes.restype = [C.POINTER(C.c_size_t), C.c_int], C.c_int
+    if lib.gava_grad_clip_struct_sizes(sizes, len(grad_clip_mirrors)) != len(grad_clip_mirrors):
+        raise GavaError("libgava_hip.so and gava_clip_amd/hip.py disagree on the number of gradient-clip ABI structs")
+    for cls, sz in zip(grad_clip_mirrors, sizes):
         if C.sizeof(cls) != sz:
             raise GavaError(f"ctypes mirror {cls.__name__} is {C.sizeof(cls)} bytes, the library's struct {sz}: gava_clip_amd/hip.py is out of "
                             f"step with include/gava_hip.h")

@@ -12,8 +12,20 @@ VitaCLIP._refresh_summary_weights nor training.refresh_vision_backward has anyth
 
 State keys and param_groups are torch.optim.AdamW's: a state_dict of either loads into the other.  The gradient is read only:
 with a GradScaler, p.grad still holds the scaled gradient after the step.
+
+Clipping by global norm is part of the step (gava_grad_norm, gava_adamw_step_clipped): torch's unscale_ + clip_grad_norm_ + step
+in four launches (two each), without writing a gradient and without a host wait.
+
+    opt = FusedAdamW(model, lr=4e-4, weight_decay=0.2, max_grad_norm=1.0)     # float("inf"): measure, do not clip
+    scaler.scale(loss).backward(); scaler.step(opt); scaler.update()
+    opt.last["grad_norm"], opt.last["clip_coef"], opt.last["nonfinite"]       # 0-dim device views; opt.grad_norms(): per parameter
+
+The norm is that of the unscaled gradients over all param groups.  A non-finite norm skips the step on the device (torch's
+clip_grad_norm_ would scale by NaN and poison every parameter).  max_grad_norm is an attribute, settable between steps; it is
+no param_groups key and no part of state_dict().
 """
 import ctypes as C
+import math
 
 import torch
 
@@ -45,6 +57,15 @@ def check_grad(p, g):
                         f"(got {g.dtype} {tuple(g.shape)} on {g.device} for {tuple(p.shape)} on {p.device})")
 
 
+def check_max_grad_norm(v):
+    """None (no clipping stage), or a positive float: finite clips, inf measures only."""
+    if v is None:
+        return None
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or math.isnan(v) or not v > 0:
+        raise GavaError(f"FusedAdamW: max_grad_norm must be None or a positive number (float('inf') measures without clipping), got {v!r}")
+    return float(v)
+
+
 def _check_flags(flags):
     for k in _REFUSED_FLAGS:
         if flags.get(k):
@@ -55,7 +76,9 @@ class FusedAdamW(torch.optim.Optimizer):
     _step_supports_amp_scaling = True      # GradScaler.step sets self.grad_scale / self.found_inf and calls step() directly
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, *, amsgrad=False, maximize=False,
-                 capturable=False, differentiable=False):
+                 capturable=False, differentiable=False, max_grad_norm=None):
+        self.max_grad_norm = max_grad_norm
+        self.last = {}           # after a step with max_grad_norm: grad_norm, clip_coef, nonfinite (views of the device stats, valid until the next step)
         _check_flags(dict(amsgrad=amsgrad, maximize=maximize, capturable=capturable, differentiable=differentiable))
         self._model = None
         if isinstance(params, torch.nn.Module):
@@ -80,6 +103,7 @@ class FusedAdamW(torch.optim.Optimizer):
         self._sig = None         # signature of every pointer in the uploaded table
         self._table = None       # (host ctypes table, device buffer, number of chunks, entries)
         self._targets = (None, {})
+        self._clip = None        # (workspace, tensor_norm, stats, parameters in table order), allocated with the table
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, **_TORCH_GROUP_DEFAULTS)
         super().__init__(params, defaults)
 
@@ -92,6 +116,24 @@ class FusedAdamW(torch.optim.Optimizer):
             check_param(p)
             self._index.setdefault(id(p), len(self._index))
         self._sig = None
+
+    @property
+    def max_grad_norm(self):
+        return self._max_grad_norm
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, v):
+        self._max_grad_norm = check_max_grad_norm(v)
+
+    def grad_norms(self):
+        """{parameter: 0-dim view of the norm of its unscaled gradient} as the last step with max_grad_norm measured it (0 for a
+        parameter that had no gradient); empty before the first such step.  Like the views in `last` they show the device
+        buffers of the current table: the next step overwrites them, or, when a gradient or a pack has moved and the table is
+        rebuilt, leaves them behind with stale values.  Read (or clone) them before the next step."""
+        if not self.last:
+            return {}
+        _ws, tensor_norm, _stats, params = self._clip
+        return {p: tensor_norm[i] for i, p in enumerate(params)}
 
     # ---- state --------------------------------------------------------------------------------------------------------
     def _step_vector(self, device):
@@ -211,6 +253,15 @@ class FusedAdamW(torch.optim.Optimizer):
             C.memmove(host.data_ptr() + tbytes, chunks, cbytes)
         dev = host.to(device, non_blocking=True)
         self._table = (tab, dev, count, tbytes)
+        self._clip = None
+        if self.max_grad_norm is not None:
+            self._build_clip_buffers(entries, device)
+
+    def _build_clip_buffers(self, entries, device):
+        """gava_grad_norm's workspace (a double per chunk and per tensor) and outputs; they live as long as the table."""
+        n, count = len(entries), self._table[2]
+        self._clip = (torch.empty(count + n, dtype=torch.float64, device=device), torch.empty(n, dtype=torch.float32, device=device),
+                      torch.empty(4, dtype=torch.float32, device=device), [p for p, _g, _gi in entries])
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -268,7 +319,21 @@ class FusedAdamW(torch.optim.Optimizer):
         # copies that were current before the step are current after it: the kernel writes the copy of every tensor it updates
         before = self._model._summary_weight_versions() if targets else None
         with torch.cuda.device(device):
-            hip.check(hip.load().gava_adamw_step(C.byref(a), hip.stream_ptr()), "gava_adamw_step")
+            if self.max_grad_norm is None:
+                hip.check(hip.load().gava_adamw_step(C.byref(a), hip.stream_ptr()), "gava_adamw_step")
+                self.last = {}
+            else:
+                if self._clip is None:      # max_grad_norm was set after the table was built
+                    self._build_clip_buffers(entries, device)
+                ws, tensor_norm, stats, _params = self._clip
+                n = hip.GradNormArgs()
+                n.table, n.table_host, n.chunks = a.table, tab, a.chunks
+                n.n_tensors, n.n_chunks, n.n_groups = a.n_tensors, a.n_chunks, a.n_groups
+                n.grad_scale, n.max_norm = a.grad_scale, self.max_grad_norm
+                n.workspace, n.tensor_norm, n.stats = ws.data_ptr(), tensor_norm.data_ptr(), stats.data_ptr()
+                hip.check(hip.load().gava_grad_norm(C.byref(n), hip.stream_ptr()), "gava_grad_norm")
+                hip.check(hip.load().gava_adamw_step_clipped(C.byref(a), stats.data_ptr(), hip.stream_ptr()), "gava_adamw_step_clipped")
+                self.last = dict(grad_norm=stats[0], clip_coef=stats[1], nonfinite=stats[2])
         torch.autograd.graph.increment_version(updated)
         if targets:
             after = self._model._summary_weight_versions()

@@ -777,6 +777,60 @@ int gava_adamw_step(const gava_adamw_args* a, gava_stream_t stream);
  * min(cap, 3) entries, returns 3. */
 int gava_optim_struct_sizes(size_t* out, int cap);
 
+/* ---- gradient clipping by global norm inside the fused step (FusedAdamW(max_grad_norm=...)) ------------------------------------
+ *
+ * gava_grad_norm measures, gava_adamw_step_clipped applies: torch's unscale_ + clip_grad_norm_(norm_type = 2) + step without
+ * writing a gradient.  Both read the table and the chunk list of gava_adamw_step (the chunk list as gava_adamw_plan writes it:
+ * in table order, either chunk form), so the norm counts exactly the elements the step updates, each once.
+ *
+ * gava_grad_norm.  For every table entry with g != NULL and every element i of it, x_i = fl32(g_i * inv_scale) with
+ * inv_scale = 1.0f / *grad_scale (1 when grad_scale is NULL): the single-precision product the step forms.  x_i * x_i is
+ * accumulated in double in a fixed order: within a lane in element order, across the 256 lanes of a chunk's workgroup through a
+ * fixed tree (one partial per chunk), the chunk partials of a tensor in chunk order, the tensors in table order.  No
+ * floating-point atomics, nothing depends on which workgroup finishes first: the same inputs give the same bits on every run
+ * and on every rank.  With total the sum over everything, all outputs DEVICE memory:
+ *   tensor_norm[i] = fl32(sqrt(sum over entry i)), n_tensors values, optional (NULL); 0 for an entry without a gradient
+ *   stats[0] = fl32(sqrt(total))
+ *   stats[1] = fl32(min(1, max_norm / (sqrt(total) + 1e-6))), evaluated in double: clip_grad_norm_'s coefficient
+ *   stats[2] = 1 if total is not finite (an inf or a NaN anywhere), else 0; when it is 1, stats[1] is written as 1
+ *   stats[3] = 0 (reserved)
+ * max_norm = +inf measures only: the coefficient is then exactly 1.  found_inf plays no part: the stats are written either way.
+ * workspace: 8 * (n_chunks + n_tensors) bytes of DEVICE memory, 8-byte aligned; every word that is read is written first in
+ * the same call, as is every output, so nothing needs a memset and nothing is carried from call to call.  At most two launches
+ * (the per-chunk sums; one workgroup for the rest) whatever n_tensors is, no allocation, no host synchronisation.  Gradients
+ * are loaded 16 bytes per lane where the address allows and element-wise elsewhere.
+ * The chunk list must be in table order (non-decreasing tensor index), as gava_adamw_plan writes it, and the DEVICE table must
+ * equal table_host: neither can be checked from the host.  Otherwise the sums are undefined (a tensor's partials are found as
+ * one range of the list; an entry the step would skip for its group index is still counted); nothing is read or written outside
+ * the table, the list, the gradients the table names and the workspace.
+ * GAVA_EINVAL, before any launch: null args, a null table or table_host with n_tensors > 0, max_norm <= 0 or NaN, n_chunks < 0,
+ * null chunks, stats or workspace with n_chunks > 0, a workspace that is not 8-byte aligned, and whatever gava_adamw_step
+ * refuses in the table.  With n_chunks == 0 the outputs that are given are still written (norm 0, coefficient 1).
+ *
+ * gava_adamw_step_clipped is gava_adamw_step with two differences: the gradient it uses is fl32(fl32(g * inv_scale) * stats[1]),
+ * the two roundings of torch's unscale-then-clip, and when stats[2] != 0 the whole step is skipped exactly as for
+ * *found_inf != 0 (not p, m, v, the step counts or any copy changes).  With stats[1] == 1 and g * inv_scale exact (grad_scale
+ * NULL or a power of two, as GradScaler's always is) it gives gava_adamw_step's bits.
+ * stats: the four DEVICE floats gava_grad_norm wrote; NULL is GAVA_EINVAL, the rest of the checks are gava_adamw_step's.
+ * Unlike torch, whose clip_grad_norm_(error_if_nonfinite = False) scales by NaN and poisons every parameter, a non-finite norm
+ * costs one skipped step. */
+typedef struct {
+  const gava_adamw_tensor* table;        /* DEVICE, n_tensors entries */
+  const gava_adamw_tensor* table_host;   /* the same entries in host memory (validation only) */
+  const gava_adamw_chunk* chunks;        /* DEVICE, n_chunks entries */
+  int n_tensors, n_chunks, n_groups, reserved;
+  const float* grad_scale;               /* device scalar, may be NULL */
+  double max_norm;
+  void* workspace;
+  float* tensor_norm;                    /* may be NULL */
+  float* stats;
+} gava_grad_norm_args;
+int gava_grad_norm(const gava_grad_norm_args* a, gava_stream_t stream);
+int gava_adamw_step_clipped(const gava_adamw_args* a, const float* stats, gava_stream_t stream);
+
+/* sizeof of gava_grad_norm_args, like gava_optim_struct_sizes.  Writes min(cap, 1) entries, returns 1. */
+int gava_grad_clip_struct_sizes(size_t* out, int cap);
+
 /* ---- gradient with respect to the input clip: the fold half of ImagePatchEmbed2D ----------------------------------------------
  *
  * The transpose of gava_patchify's index map, as one HBM-bound pass over fp32 data.  dpatch is d(embedding rows) x the patch
